@@ -2,7 +2,7 @@
 """bench.py — BASELINE.json's metric on MI355X: input GB/s of apache_log.kex over a synthetic
 Apache log that is already resident in HBM, with the kernel roofline and a CPU baseline beside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--gib G] [--program P]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--gib G] [--program P] [--dump-outputs DIR]
   N > 1: either launched as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N … bench.py --gpus N …`
   (RANK/LOCAL_RANK/WORLD_SIZE in the environment) or plainly as `python bench.py --gpus N`, which re-executes
   itself under torch.distributed.run with N ranks on 127.0.0.1.
@@ -104,6 +104,31 @@ def cpu_baseline(program, base, sample_bytes):
         os.unlink(path)
 
 
+DUMP_SAMPLE = 1 << 22   # output bytes --dump-outputs keeps over ALL ranks: 4 B (float32 value) + 8 B (float64 position) each, 48 MiB in all
+DUMP_SEED = 0x4B4C4558
+
+
+def dump_outputs(d, out, olen, m, suffix=""):
+    """What a caller of the timed path receives from one step — the output length and the output bytes — as .npy files in `d`:
+      output_length.npy      float64 [1]   bytes written
+      output_bytes.npy       float32 [k]   byte values (0-255) at the positions below
+      output_positions.npy   float64 [k]   their offsets in the output: 0 .. olen-1 when olen <= m (k = olen), else k = m distinct
+                                           sorted offsets, one drawn with a fixed seed from each of m equal strata of [0, olen)
+    m is the rank's share of DUMP_SAMPLE.  Two builds that give the same input the same output write identical files."""
+    import numpy as np
+    import torch
+    os.makedirs(d, exist_ok=True)
+    if olen <= m:
+        pos = torch.arange(olen, dtype=torch.int64)
+    else:   # stratum i = [i*olen // m, (i+1)*olen // m) is at least olen // m >= 1 bytes wide: the offsets are distinct and < olen
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        pos = torch.arange(m, dtype=torch.int64) * olen // m + torch.randint(0, olen // m, (m,), generator=g, dtype=torch.int64)
+    vals = out[pos.to(out.device)].cpu()      # (every position < olen <= out.numel())
+    np.save(os.path.join(d, "output_length%s.npy" % suffix), np.array([olen], dtype=np.float64))
+    np.save(os.path.join(d, "output_bytes%s.npy" % suffix), vals.numpy().astype(np.float32))
+    np.save(os.path.join(d, "output_positions%s.npy" % suffix), pos.numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -122,7 +147,13 @@ def main():
     ap.add_argument("--single-device", action="store_true", help="(validation) put every rank on cuda:0")
     ap.add_argument("--py-driver", action="store_true", help="boundary hand-off driven from Python over torch.distributed (kleenexlang_amd/sharded.py) "
                                                                "instead of the library's own driver (kx_run_sharded + RCCL communicator)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (DIR/<name>_rank<r>.npy with several ranks): "
+                         "the output length and the output bytes with their positions — all of them when a rank's output fits its share "
+                         "(%d / ranks), else a fixed seeded sample of that many; 48 MiB in all over every rank; see dump_outputs()" % DUMP_SAMPLE)
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: become N ranks (one per GPU) under torch.distributed.run
@@ -269,6 +300,8 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device=comm_dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if a.dump_outputs:   # (`out` still holds the last timed step's output; each rank writes its own slice)
+        dump_outputs(a.dump_outputs, out, olen, DUMP_SAMPLE // world, "_rank%d" % rank if world > 1 else "")
 
     # Bit-exact check of EVERY output byte, outside the timed region and on the device: the expected stream of
     # the replicated input is (prefix, unit × reps, suffix) built from the CPU oracle's output on ONE base chunk
