@@ -11,6 +11,7 @@
 #include <sstream>
 
 #include "../../../include/kexc_api.h"
+#include "../../../include/kexc_approx.h"
 #include "kexc.h"
 
 namespace kexc {
@@ -33,7 +34,7 @@ Compiled compileSource(const std::string& src, const std::string& srcname, const
     return out;
   }
   Prog ast = parseKleenex(src, srcname);
-  RProg rp = desugar(ast);
+  RProg rp = desugar(ast, o.metric, o.approx_mode, o.ite);
   for (int start : rp.pipeline) {
     const bool acts = stageHasActions(rp, start);   // register actions: in-band tokens + the action post-pass
     FST f = constructTransducer(rp, start, acts && o.act);   // (--act=false = compileDirect: refuses them, Commands.hs:165-168)
@@ -182,6 +183,26 @@ int kexc_compile_flags(const char* source, size_t source_len, const char* source
                        unsigned char** blob, size_t* blob_len) {
   try {
     kexc::Options o; o.opt = opt_level; o.la = lookahead != 0; o.regex = regex != 0;
+    auto c = kexc::compileSource(std::string(source, source_len), source_name ? source_name : "<memory>", o);
+    auto b = kexc::writeBlob(c.stages, c.info);
+    *blob = (unsigned char*)dupBytes(b.data(), b.size());
+    *blob_len = b.size();
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return 1;
+  }
+}
+
+// kexc_compile_flags for a Kleenex source with the approximation flags: metric 0 LCS / 1 Hamming / 2 Levenshtein (`--metric`),
+// mode 0 correction / 1 matching / 2 explicit (`--approxmode`), iterative = `--ite`
+int kexc_compile_approx(const char* source, size_t source_len, const char* source_name, int opt_level, int lookahead, int metric,
+                        int mode, int iterative, unsigned char** blob, size_t* blob_len) {
+  try {
+    if (metric < 0 || metric > 2) throw kexc::CompileError("\"" + std::to_string(metric) + "\" is not a valid approximation type");
+    if (mode < 0 || mode > 2) throw kexc::CompileError("\"" + std::to_string(mode) + "\" is not a valid approximation mode");
+    kexc::Options o; o.opt = opt_level; o.la = lookahead != 0;
+    o.metric = (kexc::ApproxMetric)metric; o.approx_mode = (kexc::ApproxMode)mode; o.ite = iterative != 0;
     auto c = kexc::compileSource(std::string(source, source_len), source_name ? source_name : "<memory>", o);
     auto b = kexc::writeBlob(c.stages, c.info);
     *blob = (unsigned char*)dupBytes(b.data(), b.size());

@@ -4,6 +4,7 @@
 //   grammar / precedence / lexing   src/KMC/Kleenex/Parser.hs:34-222
 //   regex AST consumed              src/KMC/Kleenex/Desugaring.hs:73-118
 //   desugaring + hash-consing       src/KMC/Kleenex/Desugaring.hs:44-59,125-207
+//   approximation `<k>t`            src/KMC/Kleenex/Desugaring.hs:146-149,209-229 (the rewrite: approx.cpp)
 // The regex-literal *syntax* lives in the un-vendored package
 // kmc-regexps-syntax @ 5c235fc057e25dffc1f5a3ca5a122ce1367ab594 (cabal.project:4-7);
 // the dialect accepted here is the one visible at the reference's call sites
@@ -413,6 +414,7 @@ struct Desugarer {
   std::map<std::pair<std::string, bool>, int> idents;
   std::map<std::string, int> regs;
   std::vector<std::string> regnames;
+  std::vector<ApproxSite> approx;   // the `<k>t` terms in the order they are desugared (dsApprox, reversed)
 
   int insertDecl(int i, const RTerm& t) { decls[i] = t; rev[t] = i; return i; }
   int decl(const RTerm& t) {  // Desugaring.hs:52-59 (hash-consing)
@@ -503,7 +505,14 @@ struct Desugarer {
       case Term::Star: return star(term(out, t->a), false);
       case Term::Plus: { int it = term(out, t->a); int is = star(term(out, t->a), false); return decl(seqT({it, is})); }
       case Term::Question: { int it = term(out, t->a); int ieps = decl(seqT({})); return decl(sumT({it, ieps})); }
-      case Term::Approx: throw CompileError("approximate matching <k> is not supported by this compiler");
+      case Term::Approx: {   // Desugaring.hs:146-149: under `~` the term itself; else recorded for applyApproximation
+        if (!out) return term(out, t->a);
+        const int i1 = term(out, t->a);
+        const int i2 = fresh++;
+        insertDecl(i2, seqT({i1}));   // insertApproxDecl (Desugaring.hs:46-50), through insertDecl: hash-consed too
+        approx.push_back({i1, i2, t->k});
+        return i2;
+      }
       case Term::Range: {
         int it = term(out, t->a);
         int m = t->lo < 0 ? 0 : t->lo;
@@ -551,7 +560,7 @@ RProg parseRegexProgram(const std::string& src, const std::string& srcname) {
   return rp;
 }
 
-RProg desugar(const Prog& p) {  // Desugaring.hs:173-207
+RProg desugar(const Prog& p, ApproxMetric metric, ApproxMode mode, bool ite) {  // Desugaring.hs:173-219
   Desugarer d;
   int n = 0;
   for (auto& dc : p.decls) {
@@ -573,6 +582,7 @@ RProg desugar(const Prog& p) {  // Desugaring.hs:173-207
     if (it == d.idents.end()) throw CompileError("identifier in pipeline with no declaration: " + id);
     rp.pipeline.push_back(it->second);
   }
+  applyApproximation(d.decls, d.fresh, d.approx, metric, mode, ite);   // approx.cpp
   rp.decls = std::move(d.decls);
   rp.regnames = std::move(d.regnames);
   return rp;

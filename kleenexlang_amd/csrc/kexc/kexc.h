@@ -7,6 +7,7 @@
 //   surface syntax      src/KMC/Kleenex/Parser.hs:154-222
 //   regex literals      consumer side src/KMC/Kleenex/Desugaring.hs:73-118
 //   desugaring          src/KMC/Kleenex/Desugaring.hs:125-207
+//   approximation       src/KMC/Kleenex/Desugaring.hs:209-229, Core.hs, Approximation.hs, ApproximationMetrics.hs
 //   transducer          src/KMC/SymbolicFST/Transducer.hs:57-107
 //   determinization     src/KMC/Determinization.hs:38-257, src/KMC/TreeWriter.hs
 //   optimize            src/KMC/SymbolicSST.hs:180-331
@@ -99,7 +100,22 @@ struct RTerm {  // Kleenex/Syntax.hs:95-102
   bool operator<(const RTerm& o) const;
 };
 struct RProg { std::vector<int> pipeline; std::map<int, RTerm> decls; std::vector<std::string> regnames; };
-RProg desugar(const Prog& p);
+// approximate matching (approx.cpp; ApproximationMetrics.hs:17-18, defaults Options.hs:103-128)
+enum class ApproxMetric { LCS, Hamming, Levenshtein };
+enum class ApproxMode { Correction, Matching, Explicit };
+// metric / mode / ite: how the `<k>t` terms are rewritten (Desugaring.hs:180-184,209-219); a program without them is unaffected
+RProg desugar(const Prog& p, ApproxMetric metric = ApproxMetric::LCS, ApproxMode mode = ApproxMode::Correction, bool ite = false);
+// one `<k>t` term (Desugaring.hs:46-50): i1 = the desugared t, i2 = the identifier that stands for the approximated term
+struct ApproxSite { int i1, i2, k; };
+// Core form of the sub-program reached from `start` (Core.hs:49-75); the result starts at identifier 0
+std::map<int, RTerm> stdToCore(const std::map<int, RTerm>& decls, int start);
+// The k-fold rewrite of a core-form program starting at `start` (Approximation.hs:13-20), and the iterative one: k rewrites
+// of one error each (:24-26).  New identifiers count up from `offset`, which is the new start.
+std::map<int, RTerm> approxProg(const std::map<int, RTerm>& decls, int start, int k, int offset, ApproxMetric m, ApproxMode mode);
+std::map<int, RTerm> approxProgIt(const std::map<int, RTerm>& decls, int start, int k, int offset, ApproxMetric m, ApproxMode mode);
+// Rewrites every site in the desugared declarations (applyApproximation, Desugaring.hs:209-219); `fresh` = first free id
+void applyApproximation(std::map<int, RTerm>& decls, int fresh, const std::vector<ApproxSite>& sites, ApproxMetric m,
+                        ApproxMode mode, bool ite);
 // regex flavour (`.re` / `.rx` / `--re`): the whole source is one regular expression (parseRegex, Kleenex/Parser.hs:204-206,
 // 229-230) desugared with output enabled (desugarRegex, Desugaring.hs:231-239)
 RProg parseRegexProgram(const std::string& src, const std::string& srcname);
@@ -208,6 +224,9 @@ struct Options {
   int copt = 3;
   bool regex = false;          // regex flavour: the bit-coder (kexc.hs:46-48, compileCoder Commands.hs:246-275)
   int wordsize = 8;            // --wordsize: the run-time buffer unit (Options.hs:130-144); only 8 produces defined output, see main.cpp
+  ApproxMetric metric = ApproxMetric::LCS;              // --metric LCS|Hamming|Levenshtein (Options.hs:103-115)
+  ApproxMode approx_mode = ApproxMode::Correction;      // --approxmode correction|matching|explicit (Options.hs:117-128)
+  bool ite = false;                                     // --ite: the iterative rewrite instead of the k-fold one
 };
 struct Compiled { std::vector<StageTables> stages; std::string info; std::vector<int> sst_states; };
 Compiled compileSource(const std::string& src, const std::string& srcname, const Options& o);

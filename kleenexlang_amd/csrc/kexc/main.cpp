@@ -45,6 +45,9 @@ static int usage() {
                "       kexc compile … FILE.re|FILE.rx --out BIN   |   kexc compile … --re 'REGEX' --out BIN\n"
                "                    (regex flavour: BIN writes the code of the greedy parse, one byte per choice)\n"
                "       kexc simulate|interpret [--sim lockstep|backtrack|sst] [--quiet] [--opt N] [--act[=BOOL]] FILE.kex  < in > out\n"
+               "Approximate matching (`<k>t` terms), for compile and simulate:\n"
+               "       --metric LCS|Hamming|Levenshtein (default LCS)   --approxmode correction|matching|explicit (default correction)\n"
+               "       --ite[=BOOL] (k rewrites of one error each instead of the k-fold rewrite; default false)\n"
                "                    (sst: the compiled program on the HIP engine; lockstep (default), backtrack: the FST simulators,\n"
                "                     on the CPU; `interpret` = `simulate --quiet`)\n"
                "--la defaults to false here (the reference: true, Options.hs:153): both machines write the same bytes\n"
@@ -79,13 +82,27 @@ int main(int argc, char** argv) {
       else if (key == "la") o.la = flag();
       else if (key == "act") o.act = flag();
       else if (key == "re") expr = flag();                  // the argument is the regular expression itself (Options.hs optExpressionArg)
-      else if (key == "func" || key == "sb" || key == "ite" || key == "rmidtbls") flag();
+      else if (key == "func" || key == "sb" || key == "rmidtbls") flag();
+      else if (key == "ite") o.ite = flag();
+      else if (key == "metric") {                           // Options.hs:103-115
+        const std::string m = need();
+        if (m == "LCS") o.metric = ApproxMetric::LCS;
+        else if (m == "Hamming") o.metric = ApproxMetric::Hamming;
+        else if (m == "Levenshtein") o.metric = ApproxMetric::Levenshtein;
+        else throw CompileError("\"" + m + "\" is not a valid approximation type");
+      }
+      else if (key == "approxmode") {                       // Options.hs:117-128
+        const std::string m = need();
+        if (m == "correction") o.approx_mode = ApproxMode::Correction;
+        else if (m == "matching") o.approx_mode = ApproxMode::Matching;
+        else if (m == "explicit") o.approx_mode = ApproxMode::Explicit;
+        else throw CompileError("\"" + m + "\" is not a valid approximation mode");
+      }
       else if (key == "wordsize") {                         // Options.hs:130-144
         const std::string w = need();
         if (w != "8" && w != "16" && w != "32" && w != "64") throw CompileError("\"" + w + "\" is not a valid word size");
         o.wordsize = std::stoi(w);
       }
-      else if (key == "metric" || key == "approxmode") need();
       else if (key == "sim") { sim = need(); if (sim != "lockstep" && sim != "backtrack" && sim != "sst") throw CompileError("\"" + sim + "\" is not a valid simulation type"); }
       else if (key == "copt") o.copt = std::stoi(need());
       else if (key == "out") o.out = need();

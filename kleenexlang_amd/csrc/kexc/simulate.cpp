@@ -134,7 +134,7 @@ int simulateFST(const std::string& src, const std::string& srcname, const Option
     RProg rp = parseRegexProgram(src, srcname);
     stages.push_back({constructTransducer(rp, rp.pipeline[0], false), false});
   } else {
-    RProg rp = desugar(parseKleenex(src, srcname));
+    RProg rp = desugar(parseKleenex(src, srcname), o.metric, o.approx_mode, o.ite);
     for (int start : rp.pipeline) {
       const bool acts = stageHasActions(rp, start);
       stages.push_back({constructTransducer(rp, start, acts), acts});

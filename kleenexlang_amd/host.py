@@ -242,17 +242,32 @@ def compile_source(source, name="<memory>", opt=3):
         lib.kexc_free(blob)
 
 
-def compile_flags(source, name="<memory>", opt=3, la=False, regex=False):
+APPROX_METRICS = ("LCS", "Hamming", "Levenshtein")          # --metric (Options.hs:103-115), in kexc_compile_approx's numbering
+APPROX_MODES = ("correction", "matching", "explicit")         # --approxmode (Options.hs:117-128)
+
+
+def compile_flags(source, name="<memory>", opt=3, la=False, regex=False, metric="LCS", approx_mode="correction", ite=False):
     """``kexc compile --opt N --la=BOOL`` (regex=True: ``--re``) → KXP blob.  la=True builds the reference's lookahead machine
-    (word tests) first and the tables from its path form (include/kexc_api.h::kexc_compile_flags)."""
+    (word tests) first and the tables from its path form (include/kexc_api.h::kexc_compile_flags).  metric / approx_mode / ite are
+    ``--metric`` / ``--approxmode`` / ``--ite``: how the source's ``t<k>`` terms are rewritten (include/kexc_approx.h)."""
+    if metric not in APPROX_METRICS:
+        raise CompileError('"%s" is not a valid approximation type' % metric)
+    if approx_mode not in APPROX_MODES:
+        raise CompileError('"%s" is not a valid approximation mode' % approx_mode)
     lib = load_compiler()
     if isinstance(source, str):
         source = source.encode("utf-8")
     blob = ctypes.c_void_p()
     n = ctypes.c_size_t()
-    lib.kexc_compile_flags.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                       ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
-    rc = lib.kexc_compile_flags(source, len(source), name.encode(), opt, 1 if la else 0, 1 if regex else 0, ctypes.byref(blob), ctypes.byref(n))
+    if regex or (metric, approx_mode, ite) == ("LCS", "correction", False):
+        lib.kexc_compile_flags.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+        rc = lib.kexc_compile_flags(source, len(source), name.encode(), opt, 1 if la else 0, 1 if regex else 0, ctypes.byref(blob), ctypes.byref(n))
+    else:
+        lib.kexc_compile_approx.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
+        rc = lib.kexc_compile_approx(source, len(source), name.encode(), opt, 1 if la else 0, APPROX_METRICS.index(metric),
+                                     APPROX_MODES.index(approx_mode), 1 if ite else 0, ctypes.byref(blob), ctypes.byref(n))
     if rc:
         raise CompileError(lib.kexc_last_error().decode("utf-8", "replace"))
     try:
