@@ -97,7 +97,10 @@ typedef struct kx_config {
   uint32_t act_prefix3_min;/* blocks from which the safe-point prefix runs in three steps: 0 = 65536             [KX_ACT_PREFIX3_MIN] */
   uint32_t act_lanes;      /* one lane per chunk (token-dense streams): 0 auto, 1 off, 2 on                           [KX_ACT_LANES] */
   uint32_t act_chunk;      /* wanted chunk bytes: 0 auto (2048 / 4096)                                                 [KX_ACT_CHUNK] */
-  uint32_t reserved[4];    /* must be 0 */
+  /* ---- batched runs (run time) ---- */
+  uint32_t batch_doc_max;  /* kx_run_batch: longest document the batch kernels take; longer ones go through the single-document
+                              route: 0 = 64 KiB                                                                                */
+  uint32_t reserved[3];    /* must be 0 */
 } kx_config;
 #define KX_OFF_DIRECT 1u     /* load: entries of the plain layout name their action, not the constant's pool slot    [KX_NO_DIRECT] */
 #define KX_OFF_PAIR 2u       /* load: no two-symbol table for k_forward                                                 [KX_NO_PAIR] */
@@ -184,6 +187,41 @@ void kx_host_free(void* p);
 /* stdin → stdout contract of the produced binary (crt/crt.c:294-312,107-136): reads in_fd to EOF,
  * writes the output to out_fd. */
 int kx_run_fd(kx_program* prog, int in_fd, int out_fd, kx_stats* stats);
+
+/* ---- batched runs: many independent documents in one call ------------------------------------------------------------
+ * A batch is n_docs documents; document i is the bytes d_in[d_in_off[i], d_in_off[i+1]).  d_in_off holds n_docs + 1
+ * non-decreasing offsets (d_in_off[0] need not be 0: a slice of a larger buffer is a batch; documents may start at any byte
+ * alignment; empty documents are allowed).  Every document is a whole input — it starts in the initial state, must end in a
+ * final state, and every pipeline stage runs on it — and its result is, byte for byte, what kx_run_device gives for that
+ * document alone.  All arrays live on the device; the call blocks until the result is complete.
+ *   accepted document i: its output is d_out[d_out_off[i], d_out_off[i+1]) (d_out_off: n_docs + 1 entries, an exclusive
+ *     prefix sum, d_out_off[0] = 0); d_docs[i] = {0, 0, 0}
+ *   rejected document i: its output range is empty; d_docs[i] = {fail_pos, 1, fail_stage}, fail_pos being the number
+ *     kx_run_device reports for the document alone.  Later stages do not run it.  Its neighbours' results do not change.
+ * Return codes — NOTE: 1 does not mean "no output" here, unlike kx_run_device:
+ *   0  every document was accepted
+ *   1  at least one document was rejected; the outputs of the accepted documents are complete
+ *   KX_E_CAPACITY  *out_len = the bytes needed; d_out_off and d_docs are filled.  d_out = NULL, cap = 0 is the size query.
+ *   KX_E_ARG  among others: the offsets decrease somewhere (checked on the device before anything reads a document)
+ *   < 0  other errors, as elsewhere (kx_last_error)
+ * The batch kernels take documents of at most kx_config::batch_doc_max bytes, one lane per document.  Longer documents, and
+ * EVERY document of a stage with register actions (whose replay is sequential, kx_stage_has_actions), go through the
+ * single-document driver one at a time: correct, but not fast for many small documents of such a stage (stats->docs_routed
+ * counts them).  A call leaves kx_stage_delayed_form of every stage as it found it. */
+typedef struct kx_batch_doc {
+  uint64_t fail_pos;
+  uint32_t status;      /* 0 accepted, 1 match error */
+  uint32_t fail_stage;
+} kx_batch_doc;
+typedef struct kx_batch_stats {
+  uint64_t docs, docs_rejected;
+  uint64_t docs_routed;    /* document runs that took the single-document route, summed over the stages */
+  uint64_t in_bytes, out_bytes;
+  float forward_ms, back_ms, scan_ms, emit_ms, routed_ms, total_ms;   /* HIP events, with kx_config::collect_timing; summed over the stages */
+  uint32_t reserved[4];
+} kx_batch_stats;
+int kx_run_batch(kx_program* prog, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, void* d_out, size_t cap,
+                 uint64_t* d_out_off, kx_batch_doc* d_docs, size_t* out_len, kx_batch_stats* stats, void* stream);
 
 /* ---- sharded execution: one contiguous shard of the input per GPU -------------
  * Per stage and per rank:

@@ -1,0 +1,244 @@
+// kx_batch_host.inc — host driver of batched runs (kx_run_batch, include/kxhip.h; kernels in kx_batch.inc).  Included at the
+// end of kx_engine.hip.
+//
+// Per stage: k_bforward (lane = document) → [the routed documents, one at a time, through the single-document driver] →
+// k_bback → scan of the document lengths → k_binit + k_bemit (lane = piece) + k_bplace.  Stage s + 1's batch is stage s's
+// output batch (values + offsets); a document rejected at stage s is skipped by the later stages.  Three host round trips per
+// stage (routed count, total length, end) plus one for the offset check: the call's fixed cost, whatever the number of documents.
+
+namespace {
+
+constexpr uint32_t BATCH_DOC_MAX_DEFAULT = 64u << 10;
+
+// One document through one stage on the single-document driver (runPipeline's stage body on a shard that is first and last);
+// its output is appended at a 16-byte aligned place of W.rout, *pos advanced past it.
+int batchRouteOne(kx_program* p, uint32_t st, const uint8_t* d_doc, uint64_t n, hipStream_t sm, BatchWs& W, size_t& pos, BRoute& r) {
+  Stage& S = p->stages[st];
+  const void* src = d_doc;
+  if (n && ((uintptr_t)d_doc & 15)) {   // the shard protocol wants 16-byte aligned input
+    int rc = BatchWs::ensure(W.rin, n);
+    if (rc) return rc;
+    HIPCHECK(hipMemcpyAsync(W.rin.p, d_doc, n, hipMemcpyDeviceToDevice, sm));
+    src = W.rin.p;
+  }
+  kx_shard* s = nullptr;
+  int rc = shardBegin(p, st, src, n, 1, 1, sm, &s, true);
+  if (rc) return rc;
+  struct EndOnExit { kx_shard* s; ~EndOnExit() { kx_shard_end(s); } } end_on_exit{s};
+  kx_fwd_summary fs; kx_bwd_summary bs; uint64_t ol = 0;
+  rc = kx_shard_forward(s, &fs);
+  if (!rc) rc = kx_shard_fix_head(s, 0, &fs);
+  if (rc) return rc;
+  if (fs.fail_pos != NOFAIL) { r.rejected = 1; r.fail = fs.fail_pos; r.len = 0; return 0; }
+  rc = kx_shard_backward(s, &bs);
+  if (!rc) rc = kx_shard_resolve(s, 0, &ol);
+  if (rc) return rc;
+  pos = (pos + 15) & ~(size_t)15;
+  if (!S.act) {
+    rc = BatchWs::grow(W.rout, pos, pos + ol + 16, sm);
+    if (!rc) rc = kx_shard_emit(s, (uint8_t*)W.rout.p + pos, W.rout.cap - pos);
+    if (rc) return rc;
+    r.start = pos; r.len = ol; pos += ol;
+    return 0;
+  }
+  // a token stream: emit it aside, replay the actions (the stage's ActionRunner, as runPipeline), append the result
+  rc = BatchWs::ensure(W.tok, ol + 16);
+  if (!rc) rc = kx_shard_emit(s, W.tok.p, W.tok.cap);
+  if (rc) return rc;
+  if (p->act_runners.size() < p->stages.size()) p->act_runners.resize(p->stages.size(), nullptr);
+  ActionRunner*& ar = p->act_runners[st];
+  if (!ar) { ar = new ActionRunner; ar->cfg = &p->cfg; rc = ar->init(S.act_regs); if (rc) { delete ar; ar = nullptr; return rc; } }
+  else if ((rc = ar->reset())) return rc;
+  size_t al = 0;
+  rc = BatchWs::ensure(W.tokout, ol + ar->slack());
+  if (!rc) rc = ar->run((const uint8_t*)W.tok.p, ol, (uint8_t*)W.tokout.p, &al, sm);
+  if (!rc) rc = BatchWs::grow(W.rout, pos, pos + al + 16, sm);
+  if (rc) return rc;
+  if (al) {
+    hipLaunchKernelGGL(k_copy_bytes, dim3(64), dim3(256), 0, sm, (uint8_t*)W.rout.p + pos, (const uint8_t*)W.tokout.p, (unsigned long long)al);
+    HIPCHECK(hipGetLastError());
+  }
+  r.start = pos; r.len = al; pos += al;
+  return 0;
+}
+
+// the shard drivers' per-stage engine choice (delayed form, its back-off, the entry layout), which routed documents may move
+struct DfSaved { uint32_t streak, skip; bool armed, given_up; int use_alt; };
+
+}  // namespace
+
+extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, void* d_out, size_t cap,
+                            uint64_t* d_out_off, kx_batch_doc* d_docs, size_t* out_len, kx_batch_stats* stats, void* stream) {
+  if (!p || !out_len) return setErr(KX_E_ARG, "null argument");
+  if (n_docs && (!d_in_off || !d_out_off || !d_docs)) return setErr(KX_E_ARG, "kx_run_batch: offsets, output offsets and document records are required");
+  if (n_docs >= 0xFFFFFFFFull) return setErr(KX_E_ARG, "kx_run_batch: at most 2^32 - 2 documents per call");
+  *out_len = 0;
+  kx_batch_stats bst{};
+  bst.docs = n_docs;
+  const hipStream_t sm = (hipStream_t)stream;
+  if (n_docs == 0) {
+    if (d_out_off) { HIPCHECK(hipMemsetAsync(d_out_off, 0, 8, sm)); HIPCHECK(hipStreamSynchronize(sm)); }
+    if (stats) *stats = bst;
+    return 0;
+  }
+  if (!p->batch) p->batch = new BatchWs;
+  BatchWs& W = *p->batch;
+  const bool timing = p->cfg.collect_timing != 0;
+  if (!W.have_events) {
+    for (auto& e : W.ev) HIPCHECK(hipEventCreate(&e));
+    W.have_events = true;
+  }
+  if (!W.lds_set) {   // (every stage's image fits what kx_load granted the general engine's kernels)
+    size_t lds = 0;
+    for (auto& s : p->stages) lds = s.lds_bytes > lds ? s.lds_bytes : lds;
+    for (const void* fn : {(const void*)k_bforward<false>, (const void*)k_bforward<true>, (const void*)k_bback<false>, (const void*)k_bback<true>,
+                           (const void*)k_bemit<false>, (const void*)k_bemit<true>}) {
+      int rc = setLds(fn, lds);
+      if (rc) return rc;
+    }
+    W.lds_set = true;
+  }
+  const uint32_t ns = (uint32_t)p->stages.size();
+  std::vector<DfSaved> saved(ns);
+  for (uint32_t i = 0; i < ns; ++i) {
+    const Stage& S = p->stages[i];
+    saved[i] = DfSaved{S.df_streak, S.df_skip, S.df_slow_armed, S.df_given_up, S.use_alt};
+  }
+  struct RestoreOnExit {
+    kx_program* p; std::vector<DfSaved>& v;
+    ~RestoreOnExit() {
+      for (size_t i = 0; i < v.size(); ++i) {
+        Stage& S = p->stages[i];
+        S.df_streak = v[i].streak; S.df_skip = v[i].skip; S.df_slow_armed = v[i].armed; S.df_given_up = v[i].given_up; S.use_alt = v[i].use_alt;
+      }
+    }
+  } restore{p, saved};
+
+  const uint64_t nd = n_docs;
+  const uint32_t g1024 = (uint32_t)((nd + 1 + 1023) / 1024);
+  int rc = BatchWs::ensure(W.ctr, BC_N * 8);
+  if (!rc) rc = BatchWs::ensure(W.flags, sizeof(Flags));
+  if (!rc) rc = BatchWs::ensure(W.docs, nd * sizeof(BDoc));
+  if (!rc) rc = BatchWs::ensure(W.routes, nd * sizeof(BRoute));
+  if (!rc) rc = BatchWs::ensure(W.wsum, (size_t)g1024 * 8);
+  if (!rc) rc = BatchWs::ensure(W.woff, (size_t)g1024 * 8);
+  if (rc) return rc;
+  unsigned long long* ctr = (unsigned long long*)W.ctr.p;
+  HIPCHECK(hipMemsetAsync(ctr, 0, BC_N * 8, sm));
+  // the offsets: non-decreasing, checked on the device before any kernel reads a document; the caller's records cleared
+  hipLaunchKernelGGL(k_bcheck, dim3((uint32_t)((nd + 255) / 256)), dim3(256), 0, sm, (const unsigned long long*)d_in_off, (unsigned long long)nd, d_docs, ctr);
+  HIPCHECK(hipGetLastError());
+  unsigned long long hc[BC_N] = {0, 0, 0, 0}, ends[2] = {0, 0};
+  HIPCHECK(hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipMemcpyAsync(&ends[0], d_in_off, 8, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipMemcpyAsync(&ends[1], d_in_off + nd, 8, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipStreamSynchronize(sm));
+  if (hc[BC_BADOFF] || ends[1] < ends[0]) return setErr(KX_E_ARG, "kx_run_batch: the document offsets decrease");
+  if (ends[1] > ends[0] && !d_in) return setErr(KX_E_ARG, "kx_run_batch: null input");
+  bst.in_bytes = ends[1] - ends[0];
+
+  const uint64_t doc_max = p->cfg.batch_doc_max ? p->cfg.batch_doc_max : BATCH_DOC_MAX_DEFAULT;
+  const uint32_t bgrid = (uint32_t)p->ncu * 4;
+  const uint8_t* cur = (const uint8_t*)d_in;
+  const unsigned long long* cur_off = (const unsigned long long*)d_in_off;
+  uint64_t cur_bytes = bst.in_bytes;
+  std::vector<BRoute> routes;
+  for (uint32_t st = 0; st < ns && rc == 0; ++st) {
+    Stage& S = p->stages[st];
+    const bool last = st + 1 == ns;
+    const bool wide = S.general;
+    const size_t lds = S.lds_bytes;
+    const uint64_t nchk = (cur_bytes >> 5) + nd + 2, nslots = (cur_bytes >> 6) + nd;   // (k_bback writes every piece slot below nslots)
+    rc = BatchWs::ensure(W.chk, nchk * 2);
+    if (!rc) rc = BatchWs::ensure(W.brec, (nslots + 1) * sizeof(BRec));
+    if (rc) break;
+    unsigned long long* out_off = last ? (unsigned long long*)d_out_off : nullptr;
+    if (!last) { rc = BatchWs::ensure(W.offs[st & 1], (nd + 1) * 8); if (rc) break; out_off = (unsigned long long*)W.offs[st & 1].p; }
+    BDoc* docs = (BDoc*)W.docs.p; BRec* brec = (BRec*)W.brec.p; uint16_t* chk = (uint16_t*)W.chk.p;
+    // forward: lane = document
+    HIPCHECK(hipMemsetAsync(ctr + BC_ROUTED, 0, 8, sm));
+    if (timing) HIPCHECK(hipEventRecord(W.ev[0], sm));
+    hipLaunchKernelGGL(wide ? k_bforward<true> : k_bforward<false>, dim3(bgrid), dim3(BATCH_BT), lds, sm, cur, cur_off, (unsigned long long)nd,
+                       (unsigned long long)doc_max, S.act ? 1 : 0, st, (BDoc*)W.docs.p, d_docs, chk, (BRoute*)W.routes.p, ctr, S.T);
+    if (timing) HIPCHECK(hipEventRecord(W.ev[1], sm));
+    HIPCHECK(hipGetLastError());
+    unsigned long long nr = 0;
+    HIPCHECK(hipMemcpyAsync(&nr, ctr + BC_ROUTED, 8, hipMemcpyDeviceToHost, sm));
+    HIPCHECK(hipStreamSynchronize(sm));
+    if (timing) bst.forward_ms += evMs(W.ev[0], W.ev[1]);
+    // backward: lane = document
+    if (timing) HIPCHECK(hipEventRecord(W.ev[2], sm));
+    hipLaunchKernelGGL(wide ? k_bback<true> : k_bback<false>, dim3(bgrid), dim3(BATCH_BT), lds, sm, cur, cur_off, (unsigned long long)nd, docs, chk, brec, S.T);
+    if (timing) HIPCHECK(hipEventRecord(W.ev[3], sm));
+    HIPCHECK(hipGetLastError());
+    // the routed documents, one at a time (in document order)
+    size_t rpos = 0;
+    routes.resize(nr);
+    if (nr) {
+      const auto rt0 = std::chrono::steady_clock::now();
+      HIPCHECK(hipMemcpyAsync(routes.data(), W.routes.p, nr * sizeof(BRoute), hipMemcpyDeviceToHost, sm));
+      HIPCHECK(hipStreamSynchronize(sm));
+      std::sort(routes.begin(), routes.end(), [](const BRoute& a, const BRoute& b) { return a.doc < b.doc; });
+      for (BRoute& r : routes) {
+        rc = batchRouteOne(p, st, cur + r.start, r.len, sm, W, rpos, r);
+        if (rc) break;
+      }
+      if (rc) break;
+      bst.docs_routed += nr;
+      rc = BatchWs::ensure(W.rres, nr * sizeof(BRoute));
+      if (rc) break;
+      HIPCHECK(hipMemcpyAsync(W.rres.p, routes.data(), nr * sizeof(BRoute), hipMemcpyHostToDevice, sm));
+      hipLaunchKernelGGL(k_broute_set, dim3((uint32_t)((nr + 255) / 256)), dim3(256), 0, sm, (uint32_t)nr, (const BRoute*)W.rres.p, st, docs, d_docs, ctr);
+      HIPCHECK(hipGetLastError());
+      HIPCHECK(hipStreamSynchronize(sm));
+      bst.routed_ms += (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - rt0).count();
+    }
+    // exclusive scan of the document lengths into out_off (out_off[nd] = the stage's total)
+    if (timing) HIPCHECK(hipEventRecord(W.ev[4], sm));
+    const uint32_t ng = (uint32_t)((nd + 1023) / 1024);
+    hipLaunchKernelGGL(k_bscan_reduce, dim3(ng), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (unsigned long long*)W.wsum.p);
+    hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, ng, (const unsigned long long*)W.wsum.p, (unsigned long long*)W.woff.p, (Flags*)W.flags.p);
+    hipLaunchKernelGGL(k_bscan_down, dim3(g1024), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (const unsigned long long*)W.woff.p,
+                       (const Flags*)W.flags.p, out_off);
+    if (timing) HIPCHECK(hipEventRecord(W.ev[5], sm));
+    HIPCHECK(hipGetLastError());
+    unsigned long long total = 0;
+    HIPCHECK(hipMemcpyAsync(&total, &((Flags*)W.flags.p)->total_len, 8, hipMemcpyDeviceToHost, sm));
+    HIPCHECK(hipStreamSynchronize(sm));
+    if (timing) { bst.back_ms += evMs(W.ev[2], W.ev[3]); bst.scan_ms += evMs(W.ev[4], W.ev[5]); }
+    uint8_t* dst = nullptr;
+    if (last) {
+      *out_len = total;
+      bst.out_bytes = total;
+      if (total > cap || (total && !d_out)) { rc = setErr(KX_E_CAPACITY, "output buffer too small"); break; }
+      dst = (uint8_t*)d_out;
+    } else {
+      rc = BatchWs::ensure(W.vals[st & 1], total + 16);
+      if (rc) break;
+      dst = (uint8_t*)W.vals[st & 1].p;
+    }
+    // placing: the initial constants, every piece (lane = piece), the routed documents' outputs
+    if (timing) HIPCHECK(hipEventRecord(W.ev[6], sm));
+    if (total) {
+      hipLaunchKernelGGL(k_binit, dim3(bgrid), dim3(256), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (const unsigned long long*)out_off, dst, S.T);
+      const uint64_t eg = (nslots + BATCH_BT - 1) / BATCH_BT;
+      hipLaunchKernelGGL(wide ? k_bemit<true> : k_bemit<false>, dim3((uint32_t)(eg < bgrid ? eg : bgrid)), dim3(BATCH_BT), lds, sm, cur, cur_off,
+                         (unsigned long long)nslots, (const BDoc*)docs, (const uint16_t*)chk, (const BRec*)brec, (const unsigned long long*)out_off, dst, S.T);
+      if (nr) hipLaunchKernelGGL(k_bplace, dim3((uint32_t)nr), dim3(256), 0, sm, (const BRoute*)W.rres.p, (const uint8_t*)W.rout.p, (const unsigned long long*)out_off, dst);
+    }
+    if (timing) HIPCHECK(hipEventRecord(W.ev[7], sm));
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(sm));
+    if (timing) { bst.emit_ms += evMs(W.ev[6], W.ev[7]); bst.total_ms += evMs(W.ev[0], W.ev[7]); }
+    cur = dst; cur_off = out_off; cur_bytes = total;
+  }
+  if (rc == 0 || rc == KX_E_CAPACITY) {
+    unsigned long long rej = 0;
+    HIPCHECK(hipMemcpyAsync(&rej, ctr + BC_REJECTED, 8, hipMemcpyDeviceToHost, sm));
+    HIPCHECK(hipStreamSynchronize(sm));
+    bst.docs_rejected = rej;
+    if (rc == 0 && rej) rc = KX_MATCH_ERROR;
+  }
+  if (stats) *stats = bst;
+  return rc;
+}

@@ -67,8 +67,8 @@ class KxConfig(ctypes.Structure):
                 ("collect_timing", ctypes.c_uint32), ("phase", ctypes.c_uint32), ("window_bytes", ctypes.c_uint64)] + \
                [(k, ctypes.c_uint32) for k in ("delayed_form", "delay", "merge_window", "inline_consts", "job_stride", "disable", "force",
                                                "emit_waves", "emit_half", "emit_inplace", "emit_staging", "df_backoff", "debug_flags",
-                                               "act_par_min", "act_prefix3_min", "act_lanes", "act_chunk")] + \
-               [("reserved", ctypes.c_uint32 * 4)]
+                                               "act_par_min", "act_prefix3_min", "act_lanes", "act_chunk", "batch_doc_max")] + \
+               [("reserved", ctypes.c_uint32 * 3)]
 
 
 KX_OFF_DIRECT, KX_OFF_PAIR, KX_OFF_CMPX, KX_OFF_COOP, KX_OFF_SLOW = 1, 2, 4, 8, 16
@@ -117,6 +117,63 @@ def config_from_env(env=None, **fields):
     for k, v in fields.items():
         setattr(c, k, v)
     return c
+
+
+class KxBatchDoc(ctypes.Structure):
+    """include/kxhip.h::kx_batch_doc — one document's result of kx_run_batch."""
+    _fields_ = [("fail_pos", ctypes.c_uint64), ("status", ctypes.c_uint32), ("fail_stage", ctypes.c_uint32)]
+
+
+class KxBatchStats(ctypes.Structure):
+    """include/kxhip.h::kx_batch_stats."""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("docs", "docs_rejected", "docs_routed", "in_bytes", "out_bytes")] + \
+               [(k, ctypes.c_float) for k in ("forward_ms", "back_ms", "scan_ms", "emit_ms", "routed_ms", "total_ms")] + \
+               [("reserved", ctypes.c_uint32 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+def _check_batch_args(values, offsets):
+    """What run_batch_tensor can refuse without a device: types, dtypes, shapes, and — for offsets held on the host — their
+    order and range.  Raises TypeError / ValueError."""
+    import torch
+    if not isinstance(values, torch.Tensor) or not isinstance(offsets, torch.Tensor):
+        raise TypeError("run_batch_tensor: values and offsets must be torch tensors")
+    if values.dtype != torch.uint8 or values.dim() != 1:
+        raise TypeError("run_batch_tensor: values must be a 1-D uint8 tensor (got %s, %d-D)" % (values.dtype, values.dim()))
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise TypeError("run_batch_tensor: offsets must be a 1-D int64 tensor of n_docs + 1 entries")
+    if values.numel() and values.stride(0) != 1:
+        raise ValueError("run_batch_tensor: values must be contiguous")
+    if not offsets.is_cuda:
+        check_batch_offsets(offsets.numpy(), values.numel())
+
+
+def check_batch_offsets(offsets, nvalues):
+    """Host-side check of a batch's offsets: non-decreasing, inside [0, nvalues].  Raises ValueError."""
+    import numpy as np
+    o = np.asarray(offsets, dtype=np.int64)
+    if o.ndim != 1 or o.size < 1:
+        raise ValueError("batch offsets: a 1-D array of n_docs + 1 entries")
+    if o.size > 1 and bool(np.any(o[1:] < o[:-1])):
+        raise ValueError("batch offsets: not non-decreasing (document %d)" % int(np.argmax(o[1:] < o[:-1])))
+    if int(o[0]) < 0 or int(o[-1]) > nvalues:
+        raise ValueError("batch offsets: outside the values buffer [0, %d]" % nvalues)
+
+
+def pack_batch(docs):
+    """A list of bytes-like documents → (values bytes, offsets list).  Raises TypeError for anything else."""
+    offs, total = [0], 0
+    parts = []
+    for i, d in enumerate(docs):
+        if not isinstance(d, (bytes, bytearray, memoryview)):
+            raise TypeError("run_batch: document %d is %s, not bytes" % (i, type(d).__name__))
+        b = bytes(d)
+        parts.append(b)
+        total += len(b)
+        offs.append(total)
+    return b"".join(parts), offs
 
 
 class KxDfInfo(ctypes.Structure):
@@ -203,6 +260,7 @@ def load_engine():
                                     ctypes.POINTER(KxStats)]
         lib.kx_host_free.argtypes = [vp]
         lib.kx_run_fd.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxStats)]
+        lib.kx_run_batch.argtypes = [vp, vp, vp, u64, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(KxBatchStats), vp]
         lib.kx_shard_begin.argtypes = [vp, u32, vp, sz, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(vp)]
         lib.kx_shard_forward.argtypes = [vp, ctypes.POINTER(KxFwdSummary)]
         lib.kx_shard_fix_head.argtypes = [vp, u32, ctypes.POINTER(KxFwdSummary)]
@@ -613,6 +671,76 @@ class Program:
         stream = torch.cuda.current_stream(t.device).cuda_stream
         ol = self.run_device(t.data_ptr(), n, out.data_ptr(), out.numel(), stream)
         return out[:ol]
+
+    def run_batch_tensor(self, values, offsets, out=None):
+        """Batched run (kx_run_batch): document i is values[offsets[i]:offsets[i+1]], each a whole input of the program.
+        values: CUDA uint8 tensor (any start address); offsets: int64 tensor of n_docs + 1 non-decreasing entries (on the
+        device; a host tensor is checked here and copied).  Runs on the current stream; without `out` the output is sized
+        by the capacity query (one more pass of everything but the placing).  Returns the device tensors
+        (out_values, out_offsets, status, fail_pos, fail_stage): document i's output is out_values[out_offsets[i]:out_offsets[i+1]]
+        where status[i] == 0; status 1 = rejected at stage fail_stage[i], symbol fail_pos[i] (its range is empty)."""
+        _check_batch_args(values, offsets)
+        import torch
+        if not values.is_cuda:
+            raise EngineError("run_batch_tensor: values must be on a HIP device (there is no CPU fallback)")
+        dev = values.device
+        if not offsets.is_cuda:
+            offsets = offsets.to(dev)
+        elif offsets.numel() > 1:
+            lo, hi = offsets[[0, -1]].tolist()    # the order is checked by the engine, on the device; the range here
+            if lo < 0 or hi > values.numel():
+                raise ValueError("batch offsets: outside the values buffer [0, %d]" % values.numel())
+        offsets = offsets.contiguous()
+        n = offsets.numel() - 1
+        out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        docs = torch.empty((max(n, 1), 2), dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        vptr = values.data_ptr() if values.numel() else None
+
+        def call(buf):
+            ol = ctypes.c_size_t()
+            st = KxBatchStats()
+            rc = self._lib.kx_run_batch(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
+                                        ctypes.c_void_p(buf.data_ptr() if buf is not None and buf.numel() else None),
+                                        buf.numel() if buf is not None else 0, ctypes.c_void_p(out_off.data_ptr()),
+                                        ctypes.c_void_p(docs.data_ptr()), ctypes.byref(ol), ctypes.byref(st), ctypes.c_void_p(stream))
+            self.last_batch_stats = st
+            return rc, ol.value
+
+        if out is None:
+            rc, need = call(None)
+            if rc == -3:
+                out = torch.empty(need, dtype=torch.uint8, device=dev)
+                rc, need = call(out)
+            elif rc in (0, 1):
+                out = torch.empty(0, dtype=torch.uint8, device=dev)
+        else:
+            if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()):
+                raise TypeError("run_batch_tensor: out must be a contiguous CUDA uint8 tensor")
+            rc, need = call(out)
+        if rc == -3:
+            raise EngineError("output buffer too small: need %d bytes" % need)
+        if rc not in (0, 1):
+            raise EngineError(self._err())
+        d = docs[:n]
+        return out[:need], out_off, (d[:, 1] & 0xFFFFFFFF).to(torch.int32), d[:, 0], (d[:, 1] >> 32).to(torch.int32)
+
+    def run_batch(self, docs, device=None):
+        """Convenience form of run_batch_tensor: a list of bytes → a list holding, per document, its output bytes or a
+        MatchError (pos, stage)."""
+        import torch
+        values, offs = pack_batch(docs)
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        v = torch.frombuffer(bytearray(values), dtype=torch.uint8).to(dev) if values else torch.empty(0, dtype=torch.uint8, device=dev)
+        o = torch.tensor(offs, dtype=torch.int64).to(dev)
+        out, ooff, status, fpos, fstage = self.run_batch_tensor(v, o)
+        torch.cuda.synchronize(dev)
+        ob = out.cpu().numpy().tobytes()
+        ooff, status, fpos, fstage = ooff.tolist(), status.tolist(), fpos.tolist(), fstage.tolist()
+        res = []
+        for i in range(len(offs) - 1):
+            res.append(MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]])
+        return res
 
     def out_capacity(self, n, factor=None):
         """A generous output allocation for n input bytes (callers may also size exactly via shards)."""
