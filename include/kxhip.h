@@ -223,6 +223,27 @@ typedef struct kx_batch_stats {
 int kx_run_batch(kx_program* prog, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, void* d_out, size_t cap,
                  uint64_t* d_out_off, kx_batch_doc* d_docs, size_t* out_len, kx_batch_stats* stats, void* stream);
 
+/* ---- record mode: every separator-terminated record of a stream as its own input ----------------------------------------
+ * A record is the bytes up to and including a separator byte; a non-empty tail after the last separator is a last record;
+ * empty input has no records.  Each record's result is what kx_run_device gives for it alone (every stage runs). */
+/* offsets of the records of d_in[0, n) split after every `sep` byte (a non-empty tail is a last record):
+   d_off[0] = base, d_off[i] = base + end of record i, d_off[*n_records] = base + n.  cap < *n_records + 1:
+   KX_E_CAPACITY with *n_records set (d_off = NULL, cap = 0 is the size query).  Device pointers; blocks. */
+int kx_split_records(const void* d_in, size_t n, uint8_t sep, uint64_t base, uint64_t* d_off, uint64_t cap,
+                     uint64_t* n_records, void* stream);
+
+typedef struct kx_records_stats {
+  uint64_t records, records_rejected, records_routed, in_bytes, out_bytes, windows, longest_record;
+  float split_ms, batch_ms, total_ms;   /* split_ms, batch_ms: HIP events with kx_config::collect_timing; total_ms: wall time */
+  uint32_t reserved[4];
+} kx_records_stats;
+/* the stream on in_fd in record mode: the outputs of the accepted records, in input order, to out_fd; one line
+   "Match error at input symbol S in record R!" per rejected record to report_fd (-1: none), S the record's own fail_pos,
+   R counted from 1.  Returns 0 (every record accepted), KX_MATCH_ERROR (some rejected; the rest is written in full) or an
+   error.  Windows as kx_run_fd (kx_config::window_bytes, KX_WINDOW_BYTES); kx_config::phase must be 0.  Records of a stage
+   with register actions take kx_run_batch's single-document route (records_routed): correct, not fast. */
+int kx_run_records_fd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int report_fd, kx_records_stats* stats);
+
 /* ---- sharded execution: one contiguous shard of the input per GPU -------------
  * Per stage and per rank:
  *   kx_shard_begin → kx_shard_forward → [exchange kx_fwd_summary] → kx_shard_fix_head

@@ -1,0 +1,258 @@
+// kx_records_host.inc — host side of record mode (include/kxhip.h: kx_split_records, kx_run_records_fd; kernels in
+// kx_records.inc).  Included at the end of kx_engine.hip, behind kx_batch_host.inc.
+//
+// kx_run_records_fd reuses FdStream's reader and writer threads and its buffer pool (kx_run_fd); only the compute step differs.
+// Windows are independent: per window, kx_split_records → kx_run_batch over the complete records → one output window → one
+// report line per rejected record.  The record that straddles a window's end is carried (device memory, grown as needed) and
+// run as a one-document batch in front of the next window's records.
+
+namespace {
+
+struct RecWs {   // grow-only device workspace of a split (tile counts, their offsets, the scan's Flags)
+  BatchWs::Buf tcount, toff, flags;
+  ~RecWs() { for (BatchWs::Buf* b : {&tcount, &toff, &flags}) if (b->p) (void)hipFree(b->p); }
+};
+
+// the split; *nsep = separators in the buffer, *nrec = records (nsep, or nsep + 1 with a non-empty tail)
+int splitRecords(const uint8_t* d_in, size_t n, uint8_t sep, uint64_t base, uint64_t* d_off, uint64_t cap, uint64_t* nrec,
+                 uint64_t* nsep, RecWs& W, hipStream_t sm) {
+  *nrec = 0; *nsep = 0;
+  if (n == 0) {
+    if (cap < 1) return setErr(KX_E_CAPACITY, "kx_split_records: offsets buffer too small");
+    HIPCHECK(hipMemcpyAsync(d_off, &base, 8, hipMemcpyHostToDevice, sm));
+    HIPCHECK(hipStreamSynchronize(sm));
+    return 0;
+  }
+  const uint8_t* a0 = (const uint8_t*)((uintptr_t)d_in & ~(uintptr_t)15);
+  const unsigned long long lo = (unsigned long long)(d_in - a0), hi = lo + n, ng = (hi + 15) / 16;
+  const unsigned long long ntiles = (ng + REC_TILE - 1) / REC_TILE;
+  if (ntiles > 0x7FFFFFFFull) return setErr(KX_E_ARG, "kx_split_records: buffer too large");
+  int rc = BatchWs::ensure(W.tcount, ntiles * 8);
+  if (!rc) rc = BatchWs::ensure(W.toff, ntiles * 8);
+  if (!rc) rc = BatchWs::ensure(W.flags, sizeof(Flags));
+  if (rc) return rc;
+  const uint32_t pat = 0x01010101u * sep;
+  hipLaunchKernelGGL(k_rcount, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, pat, (unsigned long long*)W.tcount.p);
+  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, (const unsigned long long*)W.tcount.p,
+                     (unsigned long long*)W.toff.p, (Flags*)W.flags.p);
+  HIPCHECK(hipGetLastError());
+  unsigned long long total = 0;
+  uint8_t lastb = 0;
+  HIPCHECK(hipMemcpyAsync(&total, &((Flags*)W.flags.p)->total_len, 8, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipMemcpyAsync(&lastb, d_in + n - 1, 1, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipStreamSynchronize(sm));
+  const int tail = lastb != sep;
+  *nsep = total;
+  *nrec = total + (uint64_t)tail;
+  if (cap < *nrec + 1 || !d_off) return setErr(KX_E_CAPACITY, "kx_split_records: offsets buffer too small");
+  hipLaunchKernelGGL(k_rwrite, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, pat, (const unsigned long long*)W.toff.p,
+                     (unsigned long long)base, total, tail, (unsigned long long*)d_off);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(sm));
+  return 0;
+}
+
+// the compute step of kx_run_records_fd
+struct RecordsRun {
+  kx_program* p = nullptr;
+  FdStream* fs = nullptr;
+  uint8_t sep = '\n';
+  int report_fd = -1;
+  RecWs ws;
+  BatchWs::Buf off, ooff, docs, carry, one, longest;   // offsets; output offsets; doc records; the straddling record; its offsets
+  uint64_t carry_len = 0, recno = 0;                   // records reported so far (R of the next record is recno + 1)
+  double ratio = 4.0;                                  // output bytes per input byte, from the previous window
+  bool rejected = false;
+  kx_records_stats st{};
+  hipEvent_t ev[4] = {};
+  bool timing = false;
+
+  ~RecordsRun() {
+    for (BatchWs::Buf* b : {&off, &ooff, &docs, &carry, &one, &longest}) if (b->p) (void)hipFree(b->p);
+    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+  }
+
+  int report(const kx_batch_doc* d, uint64_t n, uint64_t first_rec) {
+    if (report_fd < 0) return 0;
+    std::string s;
+    for (uint64_t i = 0; i < n; ++i)
+      if (d[i].status) s += "Match error at input symbol " + std::to_string(d[i].fail_pos) + " in record " + std::to_string(first_rec + i) + "!\n";
+    for (size_t w = 0; w < s.size();) {
+      const ssize_t r = write(report_fd, s.data() + w, s.size() - w);
+      if (r < 0) { if (errno == EINTR) continue; return setErr(KX_E_IO, "write of the record report failed"); }
+      w += (size_t)r;
+    }
+    return 0;
+  }
+
+  // kx_run_batch of ndocs records (offsets d_o) into *out at byte pos; a buffer too small is replaced by one of the size needed,
+  // its first pos bytes kept.  Reports the rejected records (numbered from first_rec) and advances *pos.
+  int batch(const uint8_t* in, const uint64_t* d_o, uint64_t ndocs, DevBuf* out, size_t* pos, uint64_t first_rec) {
+    if (ndocs == 0) return 0;
+    int rc = BatchWs::ensure(ooff, (ndocs + 1) * 8);
+    if (!rc) rc = BatchWs::ensure(docs, ndocs * sizeof(kx_batch_doc));
+    if (rc) return rc;
+    kx_batch_stats bs{};
+    size_t ol = 0;
+    if (timing) HIPCHECK(hipEventRecord(ev[2], nullptr));
+    rc = kx_run_batch(p, in, d_o, ndocs, out->d + *pos, out->cap - *pos, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, &ol, &bs, nullptr);
+    if (rc == KX_E_CAPACITY) {
+      DevBuf nb;
+      rc = fs->pool.get(*pos + ol + ol / 8 + 4096, &nb);
+      if (rc) return rc;
+      if (*pos) HIPCHECK(hipMemcpy(nb.d, out->d, *pos, hipMemcpyDeviceToDevice));
+      fs->pool.put(*out);
+      *out = nb;
+      rc = kx_run_batch(p, in, d_o, ndocs, out->d + *pos, out->cap - *pos, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, &ol, &bs, nullptr);
+    }
+    if (timing) { HIPCHECK(hipEventRecord(ev[3], nullptr)); HIPCHECK(hipEventSynchronize(ev[3])); st.batch_ms += evMs(ev[2], ev[3]); }
+    if (rc != 0 && rc != KX_MATCH_ERROR) return rc;
+    st.records += ndocs;
+    st.records_routed += bs.docs_routed;
+    st.out_bytes += ol;
+    *pos += ol;
+    if (bs.docs_rejected) {
+      rejected = true;
+      st.records_rejected += bs.docs_rejected;
+      std::vector<kx_batch_doc> h(ndocs);
+      HIPCHECK(hipMemcpy(h.data(), docs.p, ndocs * sizeof(kx_batch_doc), hipMemcpyDeviceToHost));
+      return report(h.data(), ndocs, first_rec);
+    }
+    return 0;
+  }
+
+  // window b (n bytes; ownership taken)
+  int window(DevBuf b, size_t n, bool last) {
+    struct PutOnExit { BufPool& pool; DevBuf& b; ~PutOnExit() { pool.put(b); } } put_in{fs->pool, b};
+    const uint8_t* in = (const uint8_t*)b.d;
+    ++st.windows;
+    st.in_bytes += n;
+    // 1. the records of the window (offsets relative to b.d)
+    uint64_t nrec = 0, nsep = 0;
+    if (off.cap < 16) { int rc = BatchWs::ensure(off, (n / 32 + 2) * 8); if (rc) return rc; }
+    if (timing) HIPCHECK(hipEventRecord(ev[0], nullptr));
+    int rc = splitRecords(in, n, sep, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, ws, nullptr);
+    if (rc == KX_E_CAPACITY) {
+      rc = BatchWs::ensure(off, (nrec + 1) * 8);
+      if (!rc) rc = splitRecords(in, n, sep, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, ws, nullptr);
+    }
+    if (rc) return rc;
+    if (timing) { HIPCHECK(hipEventRecord(ev[1], nullptr)); HIPCHECK(hipEventSynchronize(ev[1])); st.split_ms += evMs(ev[0], ev[1]); }
+    const uint64_t complete = last ? nrec : nsep;   // (a tail that is not the stream's end continues in the next window)
+    const uint64_t* d_off = (const uint64_t*)off.p;
+    // 2. the carried record: its rest is this window's first record (or all of the window, if it holds no separator)
+    if (carry_len && complete == 0 && !last) {
+      rc = BatchWs::grow(carry, carry_len, carry_len + n, nullptr);
+      if (!rc && n) HIPCHECK(hipMemcpy((uint8_t*)carry.p + carry_len, in, n, hipMemcpyDeviceToDevice));
+      if (rc) return rc;
+      carry_len += n;
+      st.longest_record = carry_len > st.longest_record ? carry_len : st.longest_record;
+      return 0;
+    }
+    DevBuf out;
+    const size_t est = (size_t)((double)(n + carry_len) * ratio) + 4096;
+    rc = fs->pool.get(est, &out);
+    if (rc) return rc;
+    struct PutOut { BufPool& pool; DevBuf& b; bool own = true; ~PutOut() { if (own) pool.put(b); } } put_out{fs->pool, out};
+    size_t pos = 0;
+    uint64_t first = 0;
+    const uint64_t in_used = n + carry_len;
+    if (carry_len) {
+      uint64_t e = 0;
+      if (complete) HIPCHECK(hipMemcpy(&e, d_off + 1, 8, hipMemcpyDeviceToHost));
+      rc = BatchWs::grow(carry, carry_len, carry_len + e, nullptr);
+      if (!rc) rc = BatchWs::ensure(one, 16);
+      if (rc) return rc;
+      if (e) HIPCHECK(hipMemcpy((uint8_t*)carry.p + carry_len, in, e, hipMemcpyDeviceToDevice));
+      carry_len += e;
+      const uint64_t o2[2] = {0, carry_len};
+      HIPCHECK(hipMemcpy(one.p, o2, 16, hipMemcpyHostToDevice));
+      st.longest_record = carry_len > st.longest_record ? carry_len : st.longest_record;
+      rc = batch((const uint8_t*)carry.p, (const uint64_t*)one.p, 1, &out, &pos, recno + 1);
+      if (rc) return rc;
+      ++recno;
+      carry_len = 0;
+      first = complete ? 1 : 0;
+    }
+    // 3. the window's complete records
+    const uint64_t nd = complete - first;
+    if (nd) {
+      rc = BatchWs::ensure(longest, 8);
+      if (rc) return rc;
+      HIPCHECK(hipMemsetAsync(longest.p, 0, 8, nullptr));
+      const uint64_t g = (nd + 255) / 256;
+      hipLaunchKernelGGL(k_rlongest, dim3((uint32_t)(g < 1024 ? g : 1024)), dim3(256), 0, nullptr, (const unsigned long long*)(d_off + first),
+                         (unsigned long long)nd, (unsigned long long*)longest.p);
+      HIPCHECK(hipGetLastError());
+      rc = batch(in, d_off + first, nd, &out, &pos, recno + 1);
+      if (rc) return rc;
+      recno += nd;
+      uint64_t lr = 0;
+      HIPCHECK(hipMemcpy(&lr, longest.p, 8, hipMemcpyDeviceToHost));
+      st.longest_record = lr > st.longest_record ? lr : st.longest_record;
+    }
+    // 4. the tail that continues in the next window
+    if (!last && nrec > nsep) {
+      uint64_t s = 0;
+      HIPCHECK(hipMemcpy(&s, d_off + nsep, 8, hipMemcpyDeviceToHost));
+      carry_len = n - s;
+      rc = BatchWs::grow(carry, 0, carry_len, nullptr);
+      if (rc) return rc;
+      HIPCHECK(hipMemcpy(carry.p, in + s, carry_len, hipMemcpyDeviceToDevice));
+    }
+    // 5. the output window
+    const uint64_t used = in_used - carry_len;
+    if (used) ratio = (double)pos / (double)used * 1.0625;
+    if (pos == 0) return 0;
+    put_out.own = false;
+    if (!fs->outq.push(FdStream::OutWin{out, pos})) { fs->pool.put(out); return KX_E_IO; }   // (closed: the writer failed; its error is reported)
+    return 0;
+  }
+};
+
+}  // namespace
+
+extern "C" int kx_split_records(const void* d_in, size_t n, uint8_t sep, uint64_t base, uint64_t* d_off, uint64_t cap, uint64_t* n_records,
+                                void* stream) {
+  if (!n_records) return setErr(KX_E_ARG, "null argument");
+  *n_records = 0;
+  if (n && !d_in) return setErr(KX_E_ARG, "kx_split_records: null input");
+  if (cap && !d_off) return setErr(KX_E_ARG, "kx_split_records: null offsets with a capacity");
+  RecWs ws;
+  uint64_t nsep = 0;
+  return splitRecords((const uint8_t*)d_in, n, sep, base, d_off, cap, n_records, &nsep, ws, (hipStream_t)stream);
+}
+
+extern "C" int kx_run_records_fd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int report_fd, kx_records_stats* stats) {
+  if (!p) return setErr(KX_E_ARG, "null argument");
+  if (p->cfg.phase) return setErr(KX_E_ARG, "record mode runs every phase: kx_config::phase must be 0");
+  const double t_begin = FdStream::nowMs();
+  FdStream fsr;
+  fsr.p = p; fsr.in_fd = in_fd; fsr.out_fd = out_fd;
+  size_t window = p->cfg.window_bytes ? p->cfg.window_bytes : (size_t)1 << 30;
+  if (const char* ev = getenv("KX_WINDOW_BYTES")) { long long v = atoll(ev); if (v > 0) window = (size_t)v; }
+  if (window < 4096) window = 4096;
+  if (fsr.CH > window) fsr.CH = (window + 4095) & ~(size_t)4095;
+  fsr.window = (window + fsr.CH - 1) / fsr.CH * fsr.CH;
+  (void)hipGetDevice(&fsr.dev);
+  RecordsRun R;
+  R.p = p; R.fs = &fsr; R.sep = sep; R.report_fd = report_fd;
+  R.timing = p->cfg.collect_timing != 0;
+  int rc = 0;
+  if (R.timing) for (auto& e : R.ev) if (hipEventCreate(&e) != hipSuccess) rc = setErr(KX_E_HIP, "hipEventCreate failed");
+  std::thread reader([&] { fsr.readerMain(); });
+  std::thread writer([&] { fsr.writerMain(); });
+  FdStream::InWin w;
+  for (;;) {
+    const bool ok = !rc && fsr.inq.pop(&w);
+    if (!ok) break;
+    rc = R.window(w.b, w.n, w.last);
+  }
+  if (rc) fsr.fail(rc); else fsr.outq.finish();
+  reader.join(); writer.join();
+  R.st.total_ms = (float)(FdStream::nowMs() - t_begin);
+  if (stats) *stats = R.st;
+  if (rc) return rc;
+  if (fsr.err) { g_err = fsr.emsg; return fsr.err; }   // (the first error, whichever thread met it)
+  return R.rejected ? KX_MATCH_ERROR : 0;
+}

@@ -8,7 +8,9 @@
 // the reference (crt.c:390-393,408-411); without it the phases of a pipeline run
 // as chained device-resident stages inside one process (instead of
 // fork()+pipe(), crt.c:414-454).  `--gpus N` (no counterpart in the reference) shards a regular
-// file on stdin over N GPUs (kx_run_fd_sharded).
+// file on stdin over N GPUs (kx_run_fd_sharded).  `--records[=SEP]` (no counterpart either) runs every SEP-terminated record
+// (default a newline) as its own input (kx_run_records_fd): the accepted records' outputs go to stdout, one
+// "Match error at input symbol S in record R!" line per rejected record to stderr, and the run goes on to the end.
 //
 // BIN = this executable ++ KXP blob ++ libdir ++ trailer (see kexc main.cpp).
 // The engine is loaded with dlopen so that this file carries no HIP dependency.
@@ -64,6 +66,26 @@ static void usage(const char* name) {
   fprintf(stdout, "- \"%s\": reads from stdin and writes to stdout.\n", name);
   fprintf(stdout, "- \"%s -i\": prints compilation info.\n", name);
   fprintf(stdout, "- \"%s -t\": runs normally, but prints timing to stderr.\n", name);
+  fprintf(stdout, "- \"%s --records[=SEP]\": runs every line (or SEP-terminated record) as its own input; rejected ones are reported on stderr.\n", name);
+}
+
+// --records=SEP: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
+static bool parseSeparator(const char* a, uint8_t* sep) {
+  auto hex = [](char c) { return c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1; };
+  const size_t n = strlen(a);
+  if (n == 1) { *sep = (uint8_t)a[0]; return true; }
+  if (n == 2 && a[0] == '\\') {
+    switch (a[1]) {
+      case 'n': *sep = '\n'; return true;
+      case 't': *sep = '\t'; return true;
+      case 'r': *sep = '\r'; return true;
+      case '0': *sep = 0; return true;
+      case '\\': *sep = '\\'; return true;
+      default: return false;
+    }
+  }
+  if (n == 4 && a[0] == '\\' && a[1] == 'x' && hex(a[2]) >= 0 && hex(a[3]) >= 0) { *sep = (uint8_t)(hex(a[2]) * 16 + hex(a[3])); return true; }
+  return false;
 }
 
 int main(int argc, char** argv) {
@@ -86,8 +108,10 @@ int main(int argc, char** argv) {
   if (fread(blob.data(), 1, bl, self) != bl || fread(&libdir[0], 1, dl, self) != dl) { fprintf(stderr, "corrupt payload\n"); return 1; }
   fclose(self);
 
-  static struct option long_options[] = {{"phase", required_argument, 0, 'p'}, {"gpus", required_argument, 0, 'g'}, {0, 0, 0, 0}};
-  bool timing = false;
+  static struct option long_options[] = {{"phase", required_argument, 0, 'p'}, {"gpus", required_argument, 0, 'g'},
+                                         {"records", optional_argument, 0, 'r'}, {0, 0, 0, 0}};
+  bool timing = false, records = false;
+  uint8_t sep = '\n';
   long phase = 0, gpus = 0;
   int c;
   while ((c = getopt_long(argc, argv, "ihtp:", long_options, nullptr)) != -1) {
@@ -103,10 +127,17 @@ int main(int argc, char** argv) {
       case 't': timing = true; break;
       case 'g': gpus = atol(optarg); if (gpus < 1 || gpus > 64) { fprintf(stderr, "Invalid number of GPUs: %ld given\n", gpus); return 1; } break;
       case 'p': phase = atol(optarg); if (phase < 1) { fprintf(stderr, "Invalid phase: %ld given\n", phase); return 1; } break;
+      case 'r':
+        records = true;
+        if (optarg && !parseSeparator(optarg, &sep)) { fprintf(stderr, "Invalid record separator: %s\n", optarg); return 1; }
+        break;
       case 'h':
       default: usage(argv[0]); return 1;
     }
   }
+  // (refused before the engine library is loaded)
+  if (records && phase) { fprintf(stderr, "%s: --records cannot be combined with --phase\n", argv[0]); return 1; }
+  if (records && gpus) { fprintf(stderr, "%s: --records cannot be combined with --gpus\n", argv[0]); return 1; }
   struct timeval t0, t1;
   if (timing) gettimeofday(&t0, nullptr);
 
@@ -121,6 +152,20 @@ int main(int argc, char** argv) {
   kx_stats st;
   int rc;
   kx_config cfg = configFromEnv();
+  if (records) {
+    auto runr = (int (*)(kx_program*, int, int, uint8_t, int, kx_records_stats*))dlsym(h, "kx_run_records_fd");
+    if (!runr) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd (--records needs a newer engine library)\n", argv[0]); return 1; }
+    kx_program* prog = nullptr;
+    if (load(blob.data(), blob.size(), &cfg, &prog)) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 1; }
+    kx_records_stats rs;
+    rc = runr(prog, STDIN_FILENO, STDOUT_FILENO, sep, STDERR_FILENO, &rs);
+    if (rc != 0 && rc != KX_MATCH_ERROR) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 1; }
+    if (timing) {   // (a rejected record does not end the run: the time is printed either way)
+      gettimeofday(&t1, nullptr);
+      fprintf(stderr, "time (ms): %ld\n", (long)((t1.tv_sec - t0.tv_sec) * 1000 + (t1.tv_usec - t0.tv_usec) / 1000));
+    }
+    return rc == KX_MATCH_ERROR ? 1 : 0;
+  }
   if (gpus) {
     auto runs = (int (*)(const void*, size_t, const kx_config*, int, int, int, kx_stats*))dlsym(h, "kx_run_fd_sharded_cfg");
     if (phase) { fprintf(stderr, "%s: --gpus cannot be combined with --phase\n", argv[0]); return 1; }

@@ -176,6 +176,78 @@ def pack_batch(docs):
     return b"".join(parts), offs
 
 
+class KxRecordsStats(ctypes.Structure):
+    """include/kxhip.h::kx_records_stats."""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("records", "records_rejected", "records_routed", "in_bytes", "out_bytes", "windows",
+                                               "longest_record")] + \
+               [(k, ctypes.c_float) for k in ("split_ms", "batch_ms", "total_ms")] + \
+               [("reserved", ctypes.c_uint32 * 4)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+def _check_sep(sep):
+    """A record separator: one byte, as bytes of length 1 or an int in [0, 255] → the int.  Raises TypeError / ValueError."""
+    if isinstance(sep, bool) or not isinstance(sep, (bytes, bytearray, int)):
+        raise TypeError("record separator: one byte (bytes of length 1 or an int), not %s" % type(sep).__name__)
+    if isinstance(sep, int):
+        if not 0 <= sep <= 255:
+            raise ValueError("record separator: %d is not a byte value" % sep)
+        return sep
+    if len(sep) != 1:
+        raise ValueError("record separator: one byte, not %d" % len(sep))
+    return sep[0]
+
+
+def split_records_model(data, sep=b"\n"):
+    """kx_split_records in pure Python: the n_records + 1 offsets of the records of `data`, each ending after a separator byte
+    (a non-empty tail is a last record; empty data has none: [0])."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError("split_records_model: data must be bytes, not %s" % type(data).__name__)
+    s = _check_sep(sep)
+    data = bytes(data)
+    offs, i = [0], data.find(bytes([s]))
+    while i >= 0:
+        offs.append(i + 1)
+        i = data.find(bytes([s]), i + 1)
+    if offs[-1] != len(data):
+        offs.append(len(data))
+    return offs
+
+
+def _check_values(values, what):
+    import torch
+    if not isinstance(values, torch.Tensor):
+        raise TypeError("%s: values must be a torch tensor, not %s" % (what, type(values).__name__))
+    if values.dtype != torch.uint8 or values.dim() != 1:
+        raise TypeError("%s: values must be a 1-D uint8 tensor (got %s, %d-D)" % (what, values.dtype, values.dim()))
+    if values.numel() and values.stride(0) != 1:
+        raise ValueError("%s: values must be contiguous" % what)
+
+
+def split_records_tensor(values, sep=b"\n"):
+    """kx_split_records: the record offsets of a CUDA uint8 tensor (any start address) as an int64 device tensor of
+    n_records + 1 entries, relative to values[0] — the offsets run_batch_tensor takes.  Runs on the current stream, blocks."""
+    _check_values(values, "split_records_tensor")
+    s = _check_sep(sep)
+    import torch
+    if not values.is_cuda:
+        raise EngineError("split_records_tensor: values must be on a HIP device (there is no CPU fallback)")
+    lib = load_engine()
+    stream = ctypes.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)
+    vptr = ctypes.c_void_p(values.data_ptr() if values.numel() else None)
+    n = ctypes.c_uint64()
+    rc = lib.kx_split_records(vptr, values.numel(), s, 0, None, 0, ctypes.byref(n), stream)
+    if rc not in (0, -3):
+        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
+    off = torch.empty(n.value + 1, dtype=torch.int64, device=values.device)
+    rc = lib.kx_split_records(vptr, values.numel(), s, 0, ctypes.c_void_p(off.data_ptr()), off.numel(), ctypes.byref(n), stream)
+    if rc:
+        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
+    return off
+
+
 class KxDfInfo(ctypes.Structure):
     """include/kxhip.h::kx_df_info — the delayed form of one stage."""
     _fields_ = [(k, ctypes.c_uint32) for k in ("available", "delay", "nstates", "nclasses", "image_bytes", "off_pool", "start_handle",
@@ -261,6 +333,8 @@ def load_engine():
         lib.kx_host_free.argtypes = [vp]
         lib.kx_run_fd.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxStats)]
         lib.kx_run_batch.argtypes = [vp, vp, vp, u64, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(KxBatchStats), vp]
+        lib.kx_split_records.argtypes = [vp, sz, ctypes.c_uint8, u64, vp, u64, ctypes.POINTER(u64), vp]
+        lib.kx_run_records_fd.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint8, ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
         lib.kx_shard_begin.argtypes = [vp, u32, vp, sz, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(vp)]
         lib.kx_shard_forward.argtypes = [vp, ctypes.POINTER(KxFwdSummary)]
         lib.kx_shard_fix_head.argtypes = [vp, u32, ctypes.POINTER(KxFwdSummary)]
@@ -741,6 +815,39 @@ class Program:
         for i in range(len(offs) - 1):
             res.append(MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]])
         return res
+
+    def run_records(self, data, sep=b"\n", device=None):
+        """Record mode on bytes: every record of `data` (split after each `sep` byte, kx_split_records on the device) is a
+        whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage)."""
+        if not isinstance(data, (bytes, bytearray, memoryview)):
+            raise TypeError("run_records: data must be bytes, not %s" % type(data).__name__)
+        _check_sep(sep)
+        import torch
+        data = bytes(data)
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        v = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else torch.empty(0, dtype=torch.uint8, device=dev)
+        offs = split_records_tensor(v, sep)
+        out, ooff, status, fpos, fstage = self.run_batch_tensor(v, offs)
+        torch.cuda.synchronize(dev)
+        ob = out.cpu().numpy().tobytes()
+        ooff, status, fpos, fstage = ooff.tolist(), status.tolist(), fpos.tolist(), fstage.tolist()
+        return [MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]] for i in range(len(status))]
+
+    def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1):
+        """kx_run_records_fd: the stream on in_fd in record mode, outputs to out_fd, one line per rejected record to report_fd
+        (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected."""
+        for name, fd in (("in_fd", in_fd), ("out_fd", out_fd), ("report_fd", report_fd)):
+            if isinstance(fd, bool) or not isinstance(fd, int):
+                raise TypeError("run_records_fd: %s must be an int file descriptor, not %s" % (name, type(fd).__name__))
+        s = _check_sep(sep)
+        st = KxRecordsStats()
+        rc = self._lib.kx_run_records_fd(self._h, in_fd, out_fd, s, report_fd, ctypes.byref(st))
+        self.last_records_stats = st
+        if rc not in (0, 1):
+            raise EngineError(self._err())
+        d = st.as_dict()
+        d["rejected"] = rc == 1
+        return d
 
     def out_capacity(self, n, factor=None):
         """A generous output allocation for n input bytes (callers may also size exactly via shards)."""
