@@ -244,6 +244,20 @@ typedef struct kx_records_stats {
    with register actions take kx_run_batch's single-document route (records_routed): correct, not fast. */
 int kx_run_records_fd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int report_fd, kx_records_stats* stats);
 
+/* ---- quote-aware record mode: a separator inside quotes ends no record ----------------------------------------------------
+ * The quote state at a byte is the parity of the `quote` bytes before it, from the start of the stream (parity_in carries it
+ * into a buffer); a `sep` byte ends a record only at even parity.  A doubled quote ("" inside a quoted field) toggles twice, so
+ * RFC 4180 splits right with no escape rule; every record boundary has even parity.  A stray unbalanced quote inverts the
+ * state for the rest of the stream (with no quote after it, the rest is one record).  Backslash escapes are not understood.
+ * quote == sep is KX_E_ARG. */
+/* kx_split_records for d_in[0, n) with quote byte `quote` and the parity at d_in[0] parity_in (0 or 1, else KX_E_ARG).  Offsets,
+   capacity and size query as kx_split_records; *parity_out (may be NULL) = parity_in ^ (quotes in the buffer & 1). */
+int kx_split_records_quoted(const void* d_in, size_t n, uint8_t sep, uint8_t quote, uint32_t parity_in, uint64_t base,
+                            uint64_t* d_off, uint64_t cap, uint64_t* n_records, uint32_t* parity_out, void* stream);
+/* kx_run_records_fd with the quoted split; the parity carries from window to window (it starts at 0). */
+int kx_run_records_fd_quoted(kx_program* p, int in_fd, int out_fd, uint8_t sep, uint8_t quote, int report_fd,
+                             kx_records_stats* stats);
+
 /* ---- sharded execution: one contiguous shard of the input per GPU -------------
  * Per stage and per rank:
  *   kx_shard_begin → kx_shard_forward → [exchange kx_fwd_summary] → kx_shard_fix_head

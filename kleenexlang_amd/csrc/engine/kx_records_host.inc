@@ -4,7 +4,8 @@
 // kx_run_records_fd reuses FdStream's reader and writer threads and its buffer pool (kx_run_fd); only the compute step differs.
 // Windows are independent: per window, kx_split_records → kx_run_batch over the complete records → one output window → one
 // report line per rejected record.  The record that straddles a window's end is carried (device memory, grown as needed) and
-// run as a one-document batch in front of the next window's records.
+// run as a one-document batch in front of the next window's records.  With a quote byte (kx_run_records_fd_quoted) the split is
+// kx_split_records_quoted, and the quote parity at the end of each window is the parity_in of the next; nothing else differs.
 
 namespace {
 
@@ -52,11 +53,68 @@ int splitRecords(const uint8_t* d_in, size_t n, uint8_t sep, uint64_t base, uint
   return 0;
 }
 
-// the compute step of kx_run_records_fd
+struct RecQWs {   // grow-only device workspace of a quoted split: RecWs (tcount = the selected counts) plus the per-tile quote counts,
+                  // their scan, the separators and the separators outside quotes from an even start; flags holds two Flags
+  RecWs base;
+  BatchWs::Buf tq, tqoff, tsep, teven;
+  ~RecQWs() { for (BatchWs::Buf* b : {&tq, &tqoff, &tsep, &teven}) if (b->p) (void)hipFree(b->p); }
+};
+
+// the quoted split (quote != sep, parity_in ≤ 1); *nsep = separators outside quotes, *nrec = records, *parity_out = parity_in ^ the
+// quote count's parity
+int splitRecordsQuoted(const uint8_t* d_in, size_t n, uint8_t sep, uint8_t quote, uint32_t parity_in, uint64_t base, uint64_t* d_off,
+                       uint64_t cap, uint64_t* nrec, uint64_t* nsep, uint32_t* parity_out, RecQWs& W, hipStream_t sm) {
+  *nrec = 0; *nsep = 0; *parity_out = parity_in;
+  if (n == 0) {
+    if (cap < 1) return setErr(KX_E_CAPACITY, "kx_split_records_quoted: offsets buffer too small");
+    HIPCHECK(hipMemcpyAsync(d_off, &base, 8, hipMemcpyHostToDevice, sm));
+    HIPCHECK(hipStreamSynchronize(sm));
+    return 0;
+  }
+  const uint8_t* a0 = (const uint8_t*)((uintptr_t)d_in & ~(uintptr_t)15);
+  const unsigned long long lo = (unsigned long long)(d_in - a0), hi = lo + n, ng = (hi + 15) / 16;
+  const unsigned long long ntiles = (ng + REC_TILE - 1) / REC_TILE;
+  if (ntiles > 0x7FFFFFFFull) return setErr(KX_E_ARG, "kx_split_records_quoted: buffer too large");
+  int rc = 0;
+  for (BatchWs::Buf* b : {&W.base.tcount, &W.base.toff, &W.tq, &W.tqoff, &W.tsep, &W.teven}) if (!rc) rc = BatchWs::ensure(*b, ntiles * 8);
+  if (!rc) rc = BatchWs::ensure(W.base.flags, 2 * sizeof(Flags));
+  if (rc) return rc;
+  const uint32_t spat = 0x01010101u * sep, qpat = 0x01010101u * quote;
+  auto U = [](BatchWs::Buf& b) { return (unsigned long long*)b.p; };
+  Flags* fl = (Flags*)W.base.flags.p;
+  hipLaunchKernelGGL(k_rqcount, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, qpat, U(W.tq), U(W.tsep), U(W.teven));
+  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, (const unsigned long long*)W.tq.p, U(W.tqoff), fl);
+  hipLaunchKernelGGL(k_rqselect, dim3((uint32_t)((ntiles + 255) / 256)), dim3(256), 0, sm, (uint32_t)ntiles, (const unsigned long long*)W.tqoff.p,
+                     (const unsigned long long*)W.tsep.p, (const unsigned long long*)W.teven.p, parity_in, U(W.base.tcount));
+  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, (const unsigned long long*)W.base.tcount.p, U(W.base.toff),
+                     fl + 1);
+  HIPCHECK(hipGetLastError());
+  unsigned long long quotes = 0, total = 0;
+  uint8_t lastb = 0;
+  HIPCHECK(hipMemcpyAsync(&quotes, &fl[0].total_len, 8, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipMemcpyAsync(&total, &fl[1].total_len, 8, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipMemcpyAsync(&lastb, d_in + n - 1, 1, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipStreamSynchronize(sm));
+  *parity_out = parity_in ^ (uint32_t)(quotes & 1u);
+  const int tail = !(lastb == sep && *parity_out == 0);   // (a last separator byte inside quotes ends no record)
+  *nsep = total;
+  *nrec = total + (uint64_t)tail;
+  if (cap < *nrec + 1 || !d_off) return setErr(KX_E_CAPACITY, "kx_split_records_quoted: offsets buffer too small");
+  hipLaunchKernelGGL(k_rqwrite, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, qpat, (const unsigned long long*)W.tqoff.p,
+                     parity_in, (const unsigned long long*)W.base.toff.p, (unsigned long long)base, total, tail, (unsigned long long*)d_off);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(sm));
+  return 0;
+}
+
+// the compute step of kx_run_records_fd and kx_run_records_fd_quoted
 struct RecordsRun {
   kx_program* p = nullptr;
   FdStream* fs = nullptr;
   uint8_t sep = '\n';
+  int quote = -1;                                      // the quote byte, -1: none (kx_run_records_fd)
+  uint32_t parity = 0;                                 // quote parity at the start of the next window
+  RecQWs qws;
   int report_fd = -1;
   RecWs ws;
   BatchWs::Buf off, ooff, docs, carry, one, longest;   // offsets; output offsets; doc records; the straddling record; its offsets
@@ -131,12 +189,18 @@ struct RecordsRun {
     uint64_t nrec = 0, nsep = 0;
     if (off.cap < 16) { int rc = BatchWs::ensure(off, (n / 32 + 2) * 8); if (rc) return rc; }
     if (timing) HIPCHECK(hipEventRecord(ev[0], nullptr));
-    int rc = splitRecords(in, n, sep, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, ws, nullptr);
+    uint32_t pout = parity;
+    auto split = [&] {
+      return quote < 0 ? splitRecords(in, n, sep, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, ws, nullptr)
+                       : splitRecordsQuoted(in, n, sep, (uint8_t)quote, parity, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, &pout, qws, nullptr);
+    };
+    int rc = split();
     if (rc == KX_E_CAPACITY) {
       rc = BatchWs::ensure(off, (nrec + 1) * 8);
-      if (!rc) rc = splitRecords(in, n, sep, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, ws, nullptr);
+      if (!rc) rc = split();
     }
     if (rc) return rc;
+    parity = pout;
     if (timing) { HIPCHECK(hipEventRecord(ev[1], nullptr)); HIPCHECK(hipEventSynchronize(ev[1])); st.split_ms += evMs(ev[0], ev[1]); }
     const uint64_t complete = last ? nrec : nsep;   // (a tail that is not the stream's end continues in the next window)
     const uint64_t* d_off = (const uint64_t*)off.p;
@@ -223,7 +287,28 @@ extern "C" int kx_split_records(const void* d_in, size_t n, uint8_t sep, uint64_
   return splitRecords((const uint8_t*)d_in, n, sep, base, d_off, cap, n_records, &nsep, ws, (hipStream_t)stream);
 }
 
-extern "C" int kx_run_records_fd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int report_fd, kx_records_stats* stats) {
+extern "C" int kx_split_records_quoted(const void* d_in, size_t n, uint8_t sep, uint8_t quote, uint32_t parity_in, uint64_t base,
+                                       uint64_t* d_off, uint64_t cap, uint64_t* n_records, uint32_t* parity_out, void* stream) {
+  if (!n_records) return setErr(KX_E_ARG, "null argument");
+  *n_records = 0;
+  if (parity_out) *parity_out = 0;
+  if (quote == sep) return setErr(KX_E_ARG, "kx_split_records_quoted: the quote byte cannot be the separator");
+  if (parity_in > 1) return setErr(KX_E_ARG, "kx_split_records_quoted: parity_in must be 0 or 1");
+  if (n && !d_in) return setErr(KX_E_ARG, "kx_split_records_quoted: null input");
+  if (cap && !d_off) return setErr(KX_E_ARG, "kx_split_records_quoted: null offsets with a capacity");
+  RecQWs ws;
+  uint64_t nsep = 0;
+  uint32_t po = parity_in;
+  const int rc = splitRecordsQuoted((const uint8_t*)d_in, n, sep, quote, parity_in, base, d_off, cap, n_records, &nsep, &po, ws,
+                                    (hipStream_t)stream);
+  if (parity_out && (rc == 0 || rc == KX_E_CAPACITY)) *parity_out = po;
+  return rc;
+}
+
+namespace {
+
+// kx_run_records_fd (quote < 0) and kx_run_records_fd_quoted
+int runRecordsFd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, int report_fd, kx_records_stats* stats) {
   if (!p) return setErr(KX_E_ARG, "null argument");
   if (p->cfg.phase) return setErr(KX_E_ARG, "record mode runs every phase: kx_config::phase must be 0");
   const double t_begin = FdStream::nowMs();
@@ -236,7 +321,7 @@ extern "C" int kx_run_records_fd(kx_program* p, int in_fd, int out_fd, uint8_t s
   fsr.window = (window + fsr.CH - 1) / fsr.CH * fsr.CH;
   (void)hipGetDevice(&fsr.dev);
   RecordsRun R;
-  R.p = p; R.fs = &fsr; R.sep = sep; R.report_fd = report_fd;
+  R.p = p; R.fs = &fsr; R.sep = sep; R.quote = quote; R.report_fd = report_fd;
   R.timing = p->cfg.collect_timing != 0;
   int rc = 0;
   if (R.timing) for (auto& e : R.ev) if (hipEventCreate(&e) != hipSuccess) rc = setErr(KX_E_HIP, "hipEventCreate failed");
@@ -255,4 +340,16 @@ extern "C" int kx_run_records_fd(kx_program* p, int in_fd, int out_fd, uint8_t s
   if (rc) return rc;
   if (fsr.err) { g_err = fsr.emsg; return fsr.err; }   // (the first error, whichever thread met it)
   return R.rejected ? KX_MATCH_ERROR : 0;
+}
+
+}  // namespace
+
+extern "C" int kx_run_records_fd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int report_fd, kx_records_stats* stats) {
+  return runRecordsFd(p, in_fd, out_fd, sep, -1, report_fd, stats);
+}
+
+extern "C" int kx_run_records_fd_quoted(kx_program* p, int in_fd, int out_fd, uint8_t sep, uint8_t quote, int report_fd,
+                                        kx_records_stats* stats) {
+  if (quote == sep) return setErr(KX_E_ARG, "kx_run_records_fd_quoted: the quote byte cannot be the separator");
+  return runRecordsFd(p, in_fd, out_fd, sep, quote, report_fd, stats);
 }

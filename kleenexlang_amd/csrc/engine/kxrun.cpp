@@ -10,7 +10,8 @@
 // fork()+pipe(), crt.c:414-454).  `--gpus N` (no counterpart in the reference) shards a regular
 // file on stdin over N GPUs (kx_run_fd_sharded).  `--records[=SEP]` (no counterpart either) runs every SEP-terminated record
 // (default a newline) as its own input (kx_run_records_fd): the accepted records' outputs go to stdout, one
-// "Match error at input symbol S in record R!" line per rejected record to stderr, and the run goes on to the end.
+// "Match error at input symbol S in record R!" line per rejected record to stderr, and the run goes on to the end.  With
+// `--quote[=Q]` (default a double quote) a separator inside Q-quoted fields ends no record (kx_run_records_fd_quoted).
 //
 // BIN = this executable ++ KXP blob ++ libdir ++ trailer (see kexc main.cpp).
 // The engine is loaded with dlopen so that this file carries no HIP dependency.
@@ -67,9 +68,10 @@ static void usage(const char* name) {
   fprintf(stdout, "- \"%s -i\": prints compilation info.\n", name);
   fprintf(stdout, "- \"%s -t\": runs normally, but prints timing to stderr.\n", name);
   fprintf(stdout, "- \"%s --records[=SEP]\": runs every line (or SEP-terminated record) as its own input; rejected ones are reported on stderr.\n", name);
+  fprintf(stdout, "- \"%s --records[=SEP] --quote[=Q]\": the same, but a SEP inside Q-quoted fields (default Q: \") ends no record.\n", name);
 }
 
-// --records=SEP: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
+// --records=SEP, --quote=Q: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
 static bool parseSeparator(const char* a, uint8_t* sep) {
   auto hex = [](char c) { return c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1; };
   const size_t n = strlen(a);
@@ -109,9 +111,9 @@ int main(int argc, char** argv) {
   fclose(self);
 
   static struct option long_options[] = {{"phase", required_argument, 0, 'p'}, {"gpus", required_argument, 0, 'g'},
-                                         {"records", optional_argument, 0, 'r'}, {0, 0, 0, 0}};
-  bool timing = false, records = false;
-  uint8_t sep = '\n';
+                                         {"records", optional_argument, 0, 'r'}, {"quote", optional_argument, 0, 'q'}, {0, 0, 0, 0}};
+  bool timing = false, records = false, quoted = false;
+  uint8_t sep = '\n', quote = '"';
   long phase = 0, gpus = 0;
   int c;
   while ((c = getopt_long(argc, argv, "ihtp:", long_options, nullptr)) != -1) {
@@ -131,6 +133,10 @@ int main(int argc, char** argv) {
         records = true;
         if (optarg && !parseSeparator(optarg, &sep)) { fprintf(stderr, "Invalid record separator: %s\n", optarg); return 1; }
         break;
+      case 'q':
+        quoted = true;
+        if (optarg && !parseSeparator(optarg, &quote)) { fprintf(stderr, "Invalid quote character: %s\n", optarg); return 1; }
+        break;
       case 'h':
       default: usage(argv[0]); return 1;
     }
@@ -138,6 +144,8 @@ int main(int argc, char** argv) {
   // (refused before the engine library is loaded)
   if (records && phase) { fprintf(stderr, "%s: --records cannot be combined with --phase\n", argv[0]); return 1; }
   if (records && gpus) { fprintf(stderr, "%s: --records cannot be combined with --gpus\n", argv[0]); return 1; }
+  if (quoted && !records) { fprintf(stderr, "%s: --quote needs --records\n", argv[0]); return 1; }
+  if (quoted && quote == sep) { fprintf(stderr, "%s: the quote character cannot be the record separator\n", argv[0]); return 1; }
   struct timeval t0, t1;
   if (timing) gettimeofday(&t0, nullptr);
 
@@ -155,10 +163,12 @@ int main(int argc, char** argv) {
   if (records) {
     auto runr = (int (*)(kx_program*, int, int, uint8_t, int, kx_records_stats*))dlsym(h, "kx_run_records_fd");
     if (!runr) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd (--records needs a newer engine library)\n", argv[0]); return 1; }
+    auto runq = (int (*)(kx_program*, int, int, uint8_t, uint8_t, int, kx_records_stats*))dlsym(h, "kx_run_records_fd_quoted");
+    if (quoted && !runq) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_quoted (--quote needs a newer engine library)\n", argv[0]); return 1; }
     kx_program* prog = nullptr;
     if (load(blob.data(), blob.size(), &cfg, &prog)) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 1; }
     kx_records_stats rs;
-    rc = runr(prog, STDIN_FILENO, STDOUT_FILENO, sep, STDERR_FILENO, &rs);
+    rc = quoted ? runq(prog, STDIN_FILENO, STDOUT_FILENO, sep, quote, STDERR_FILENO, &rs) : runr(prog, STDIN_FILENO, STDOUT_FILENO, sep, STDERR_FILENO, &rs);
     if (rc != 0 && rc != KX_MATCH_ERROR) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 1; }
     if (timing) {   // (a rejected record does not end the run: the time is printed either way)
       gettimeofday(&t1, nullptr);

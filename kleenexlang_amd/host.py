@@ -187,30 +187,66 @@ class KxRecordsStats(ctypes.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+def _one_byte(v, what):
+    """One byte, as bytes of length 1 or an int in [0, 255] → the int.  Raises TypeError / ValueError naming `what`."""
+    if isinstance(v, bool) or not isinstance(v, (bytes, bytearray, int)):
+        raise TypeError("%s: one byte (bytes of length 1 or an int), not %s" % (what, type(v).__name__))
+    if isinstance(v, int):
+        if not 0 <= v <= 255:
+            raise ValueError("%s: %d is not a byte value" % (what, v))
+        return v
+    if len(v) != 1:
+        raise ValueError("%s: one byte, not %d" % (what, len(v)))
+    return v[0]
+
+
 def _check_sep(sep):
     """A record separator: one byte, as bytes of length 1 or an int in [0, 255] → the int.  Raises TypeError / ValueError."""
-    if isinstance(sep, bool) or not isinstance(sep, (bytes, bytearray, int)):
-        raise TypeError("record separator: one byte (bytes of length 1 or an int), not %s" % type(sep).__name__)
-    if isinstance(sep, int):
-        if not 0 <= sep <= 255:
-            raise ValueError("record separator: %d is not a byte value" % sep)
-        return sep
-    if len(sep) != 1:
-        raise ValueError("record separator: one byte, not %d" % len(sep))
-    return sep[0]
+    return _one_byte(sep, "record separator")
 
 
-def split_records_model(data, sep=b"\n"):
+def _check_quote(quote, sep):
+    """A quote character for the separator `sep`: one byte as _check_sep takes it, not the separator → the int."""
+    q = _one_byte(quote, "quote character")
+    if q == _check_sep(sep):
+        raise ValueError("quote character: %r is also the record separator" % bytes([q]))
+    return q
+
+
+def _check_parity(parity):
+    if isinstance(parity, bool) or not isinstance(parity, int):
+        raise TypeError("parity: 0 or 1, not %s" % type(parity).__name__)
+    if parity not in (0, 1):
+        raise ValueError("parity: 0 or 1, not %d" % parity)
+    return parity
+
+
+def split_records_model(data, sep=b"\n", quote=None, parity=0):
     """kx_split_records in pure Python: the n_records + 1 offsets of the records of `data`, each ending after a separator byte
-    (a non-empty tail is a last record; empty data has none: [0])."""
+    (a non-empty tail is a last record; empty data has none: [0]).
+
+    With a `quote` byte (kx_split_records_quoted) a separator ends a record only outside quotes: where the parity of the quote
+    bytes before it, counted from `parity` at data[0], is even.  A doubled quote toggles twice, so RFC 4180 needs no escape rule;
+    the parity after the data is parity ^ (data.count(quote) & 1)."""
     if not isinstance(data, (bytes, bytearray, memoryview)):
         raise TypeError("split_records_model: data must be bytes, not %s" % type(data).__name__)
     s = _check_sep(sep)
+    _check_parity(parity)
     data = bytes(data)
-    offs, i = [0], data.find(bytes([s]))
-    while i >= 0:
-        offs.append(i + 1)
-        i = data.find(bytes([s]), i + 1)
+    if quote is None:
+        offs, i = [0], data.find(bytes([s]))
+        while i >= 0:
+            offs.append(i + 1)
+            i = data.find(bytes([s]), i + 1)
+    else:
+        import re
+        q = _check_quote(quote, sep)
+        offs, p = [0], parity
+        for m in re.finditer(b"[" + re.escape(bytes([q])) + re.escape(bytes([s])) + b"]", data):   # (only quotes and separators)
+            if data[m.start()] == q:
+                p ^= 1
+            elif p == 0:
+                offs.append(m.start() + 1)
     if offs[-1] != len(data):
         offs.append(len(data))
     return offs
@@ -246,6 +282,29 @@ def split_records_tensor(values, sep=b"\n"):
     if rc:
         raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
     return off
+
+
+def split_quoted_records_tensor(values, sep=b"\n", quote=b'"', parity=0):
+    """kx_split_records_quoted: split_records_tensor where a separator inside quotes ends no record (split_records_model's
+    `quote`).  `parity` is the quote parity at values[0].  Returns (offsets, parity after the last byte)."""
+    _check_values(values, "split_quoted_records_tensor")
+    s, q, par = _check_sep(sep), _check_quote(quote, sep), _check_parity(parity)
+    import torch
+    if not values.is_cuda:
+        raise EngineError("split_quoted_records_tensor: values must be on a HIP device (there is no CPU fallback)")
+    lib = load_engine()
+    stream = ctypes.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)
+    vptr = ctypes.c_void_p(values.data_ptr() if values.numel() else None)
+    n, pout = ctypes.c_uint64(), ctypes.c_uint32()
+    rc = lib.kx_split_records_quoted(vptr, values.numel(), s, q, par, 0, None, 0, ctypes.byref(n), ctypes.byref(pout), stream)
+    if rc not in (0, -3):
+        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
+    off = torch.empty(n.value + 1, dtype=torch.int64, device=values.device)
+    rc = lib.kx_split_records_quoted(vptr, values.numel(), s, q, par, 0, ctypes.c_void_p(off.data_ptr()), off.numel(), ctypes.byref(n),
+                                     ctypes.byref(pout), stream)
+    if rc:
+        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
+    return off, pout.value
 
 
 class KxDfInfo(ctypes.Structure):
@@ -335,6 +394,10 @@ def load_engine():
         lib.kx_run_batch.argtypes = [vp, vp, vp, u64, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(KxBatchStats), vp]
         lib.kx_split_records.argtypes = [vp, sz, ctypes.c_uint8, u64, vp, u64, ctypes.POINTER(u64), vp]
         lib.kx_run_records_fd.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint8, ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
+        lib.kx_split_records_quoted.argtypes = [vp, sz, ctypes.c_uint8, ctypes.c_uint8, u32, u64, vp, u64, ctypes.POINTER(u64),
+                                                ctypes.POINTER(u32), vp]
+        lib.kx_run_records_fd_quoted.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_int,
+                                                 ctypes.POINTER(KxRecordsStats)]
         lib.kx_shard_begin.argtypes = [vp, u32, vp, sz, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(vp)]
         lib.kx_shard_forward.argtypes = [vp, ctypes.POINTER(KxFwdSummary)]
         lib.kx_shard_fix_head.argtypes = [vp, u32, ctypes.POINTER(KxFwdSummary)]
@@ -816,32 +879,40 @@ class Program:
             res.append(MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]])
         return res
 
-    def run_records(self, data, sep=b"\n", device=None):
+    def run_records(self, data, sep=b"\n", device=None, quote=None):
         """Record mode on bytes: every record of `data` (split after each `sep` byte, kx_split_records on the device) is a
-        whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage)."""
+        whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage).  With a `quote` byte
+        a separator inside quotes ends no record (kx_split_records_quoted from parity 0)."""
         if not isinstance(data, (bytes, bytearray, memoryview)):
             raise TypeError("run_records: data must be bytes, not %s" % type(data).__name__)
         _check_sep(sep)
+        if quote is not None:
+            _check_quote(quote, sep)
         import torch
         data = bytes(data)
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         v = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else torch.empty(0, dtype=torch.uint8, device=dev)
-        offs = split_records_tensor(v, sep)
+        offs = split_records_tensor(v, sep) if quote is None else split_quoted_records_tensor(v, sep, quote)[0]
         out, ooff, status, fpos, fstage = self.run_batch_tensor(v, offs)
         torch.cuda.synchronize(dev)
         ob = out.cpu().numpy().tobytes()
         ooff, status, fpos, fstage = ooff.tolist(), status.tolist(), fpos.tolist(), fstage.tolist()
         return [MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]] for i in range(len(status))]
 
-    def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1):
+    def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None):
         """kx_run_records_fd: the stream on in_fd in record mode, outputs to out_fd, one line per rejected record to report_fd
-        (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected."""
+        (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected.  With a `quote`
+        byte, kx_run_records_fd_quoted: a separator inside quotes ends no record."""
         for name, fd in (("in_fd", in_fd), ("out_fd", out_fd), ("report_fd", report_fd)):
             if isinstance(fd, bool) or not isinstance(fd, int):
                 raise TypeError("run_records_fd: %s must be an int file descriptor, not %s" % (name, type(fd).__name__))
         s = _check_sep(sep)
+        q = None if quote is None else _check_quote(quote, sep)
         st = KxRecordsStats()
-        rc = self._lib.kx_run_records_fd(self._h, in_fd, out_fd, s, report_fd, ctypes.byref(st))
+        if q is None:
+            rc = self._lib.kx_run_records_fd(self._h, in_fd, out_fd, s, report_fd, ctypes.byref(st))
+        else:
+            rc = self._lib.kx_run_records_fd_quoted(self._h, in_fd, out_fd, s, q, report_fd, ctypes.byref(st))
         self.last_records_stats = st
         if rc not in (0, 1):
             raise EngineError(self._err())

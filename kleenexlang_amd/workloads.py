@@ -8,6 +8,8 @@ Shapes follow the reference's own data:
   datetime     lines like test/data/datetime/gen_datetime.pl:22-45
   numbers      digit lines like test/data/numbers/gen_numbers.pl (never an empty first line)
   digits       BASELINE config 1: random ASCII digits, optionally newline-terminated
+  rfc4180      RFC 4180 rows with quoted commas, "", quoted LF / CRLF line breaks and LF / CRLF row ends (no program of
+               programs/ reads it: examples/csv_rfc4180.kex with quote-aware record mode)
 Large inputs are a seeded base chunk replicated (the reference's own method for its big log,
 test/data/apache_log/generate_big_log.sh:4-5); `tiled_expected` states what the output of a
 replicated input must be in terms of the base chunk's output, which lets full-size runs be
@@ -69,7 +71,34 @@ def numbers_line(r):
     return "".join(r.choice("0123456789") for _ in range(r.randint(1, 1000))) + "\n"
 
 
-_LINE = {"apache_log": apache_log_line, "csv": csv_row, "datetime": datetime_line, "numbers": numbers_line}
+_FIELDCH = _ALPHA + "0123456789 .-_/:;@"
+
+
+def rfc4180_row(r):
+    """One RFC 4180 row for quote-aware record mode (examples/csv_rfc4180.kex): 1-8 fields, bare (maybe empty) or quoted; quoted
+    ones may hold commas, "" and, in about 10 % of rows, an LF or CRLF line break; the row ends in LF or CRLF."""
+    broken = r.random() < 0.1
+    fields = []
+    for _ in range(r.randint(1, 8)):
+        u = r.random()
+        if u < 0.15:
+            fields.append("")
+        elif u < 0.55:
+            fields.append(_word(r, 1, 14, _FIELDCH))
+        else:
+            parts = [_word(r, 0, 10, _FIELDCH) for _ in range(r.randint(1, 4))]
+            fields.append('"' + "".join(p + r.choice([",", '""', " ", ", "]) for p in parts[:-1]) + parts[-1] + '"')
+    if broken:   # a line break inside one quoted field (a new one if the row has none)
+        k = r.randrange(len(fields))
+        br = r.choice(["\n", "\r\n"])
+        if fields[k].startswith('"'):
+            fields[k] = fields[k][:-1] + br + _word(r, 0, 8, _FIELDCH) + '"'
+        else:
+            fields[k] = '"' + fields[k] + br + _word(r, 0, 8, _FIELDCH) + '"'
+    return ",".join(fields) + r.choice(["\n", "\n", "\n", "\r\n"])
+
+
+_LINE = {"apache_log": apache_log_line, "csv": csv_row, "datetime": datetime_line, "numbers": numbers_line, "rfc4180": rfc4180_row}
 # which input shape each workload program consumes
 PROGRAM_INPUT = {"apache_log": "apache_log", "csv2json": "csv", "iso_datetime_to_json": "datetime",
                  "thousand_sep": "numbers"}
