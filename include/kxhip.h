@@ -248,8 +248,8 @@ int kx_run_records_fd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int rep
  * The quote state at a byte is the parity of the `quote` bytes before it, from the start of the stream (parity_in carries it
  * into a buffer); a `sep` byte ends a record only at even parity.  A doubled quote ("" inside a quoted field) toggles twice, so
  * RFC 4180 splits right with no escape rule; every record boundary has even parity.  A stray unbalanced quote inverts the
- * state for the rest of the stream (with no quote after it, the rest is one record).  Backslash escapes are not understood.
- * quote == sep is KX_E_ARG. */
+ * state for the rest of the stream (with no quote after it, the rest is one record).  Backslash escapes are not understood
+ * here: kx_split_records_escaped / kx_run_records_fd_escaped below add them.  quote == sep is KX_E_ARG. */
 /* kx_split_records for d_in[0, n) with quote byte `quote` and the parity at d_in[0] parity_in (0 or 1, else KX_E_ARG).  Offsets,
    capacity and size query as kx_split_records; *parity_out (may be NULL) = parity_in ^ (quotes in the buffer & 1). */
 int kx_split_records_quoted(const void* d_in, size_t n, uint8_t sep, uint8_t quote, uint32_t parity_in, uint64_t base,
@@ -257,6 +257,21 @@ int kx_split_records_quoted(const void* d_in, size_t n, uint8_t sep, uint8_t quo
 /* kx_run_records_fd with the quoted split; the parity carries from window to window (it starts at 0). */
 int kx_run_records_fd_quoted(kx_program* p, int in_fd, int out_fd, uint8_t sep, uint8_t quote, int report_fd,
                              kx_records_stats* stats);
+
+/* ---- escape-aware record mode: an escaped byte is only data ----------------------------------------------------------------
+ * An unescaped `escape` byte E escapes the next byte; an escaped byte is never a separator, a quote or an escape (so E E is a
+ * literal E, and the byte after it is live again).  Escapes apply inside and outside quotes; nothing is stripped.  `quote` is a
+ * byte value or -1 (no quotes); with one, a separator ends a record only if it is unescaped and at even parity of the unescaped
+ * quotes before it.  The state at a byte: bit 0 the quote parity (0 without a quote), bit 1 the byte is escaped; state_in gives
+ * it at d_in[0] and carries it into a buffer.  escape == sep, escape == quote, quote == sep, quote outside [-1, 255], state_in > 3
+ * or bit 0 of state_in without a quote are KX_E_ARG. */
+/* kx_split_records for d_in[0, n) with the escape byte `escape`, the quote byte `quote` (-1: none) and the state at d_in[0]
+   state_in.  Offsets, capacity and size query as kx_split_records; *state_out (may be NULL) = the state after the last byte. */
+int kx_split_records_escaped(const void* d_in, size_t n, uint8_t sep, int quote, uint8_t escape, uint32_t state_in, uint64_t base,
+                             uint64_t* d_off, uint64_t cap, uint64_t* n_records, uint32_t* state_out, void* stream);
+/* kx_run_records_fd with the escaped split; the state carries from window to window (it starts at 0). */
+int kx_run_records_fd_escaped(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, uint8_t escape, int report_fd,
+                              kx_records_stats* stats);
 
 /* ---- sharded execution: one contiguous shard of the input per GPU -------------
  * Per stage and per rank:

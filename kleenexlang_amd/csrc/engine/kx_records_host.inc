@@ -6,6 +6,8 @@
 // report line per rejected record.  The record that straddles a window's end is carried (device memory, grown as needed) and
 // run as a one-document batch in front of the next window's records.  With a quote byte (kx_run_records_fd_quoted) the split is
 // kx_split_records_quoted, and the quote parity at the end of each window is the parity_in of the next; nothing else differs.
+// With an escape byte (kx_run_records_fd_escaped) the split is kx_split_records_escaped, and the state it ends in (quote parity,
+// escape) is the state_in of the next window's split.
 
 namespace {
 
@@ -107,14 +109,75 @@ int splitRecordsQuoted(const uint8_t* d_in, size_t n, uint8_t sep, uint8_t quote
   return 0;
 }
 
-// the compute step of kx_run_records_fd and kx_run_records_fd_quoted
+struct RecEWs {   // grow-only device workspace of an escaped split: RecQWs plus the per-tile flag words and the info word
+  RecQWs q;
+  BatchWs::Buf tflag, info;
+  ~RecEWs() { for (BatchWs::Buf* b : {&tflag, &info}) if (b->p) (void)hipFree(b->p); }
+};
+
+// the escaped split (escape != sep, escape != quote, quote != sep; quote < 0: none; state_in ≤ 3, bit 0 only with a quote);
+// *nsep = valid separators, *nrec = records, *state_out = the quote parity (bit 0) and the escape state (bit 1) after the buffer
+int splitRecordsEscaped(const uint8_t* d_in, size_t n, uint8_t sep, int quote, uint8_t escape, uint32_t state_in, uint64_t base,
+                        uint64_t* d_off, uint64_t cap, uint64_t* nrec, uint64_t* nsep, uint32_t* state_out, RecEWs& W, hipStream_t sm) {
+  *nrec = 0; *nsep = 0; *state_out = state_in;
+  if (n == 0) {
+    if (cap < 1) return setErr(KX_E_CAPACITY, "kx_split_records_escaped: offsets buffer too small");
+    HIPCHECK(hipMemcpyAsync(d_off, &base, 8, hipMemcpyHostToDevice, sm));
+    HIPCHECK(hipStreamSynchronize(sm));
+    return 0;
+  }
+  const uint8_t* a0 = (const uint8_t*)((uintptr_t)d_in & ~(uintptr_t)15);
+  const unsigned long long lo = (unsigned long long)(d_in - a0), hi = lo + n, ng = (hi + 15) / 16;
+  const unsigned long long ntiles = (ng + REC_TILE - 1) / REC_TILE;
+  if (ntiles > 0x7FFFFFFFull) return setErr(KX_E_ARG, "kx_split_records_escaped: buffer too large");
+  RecQWs& Q = W.q;
+  int rc = 0;
+  for (BatchWs::Buf* b : {&Q.base.tcount, &Q.base.toff, &Q.tq, &Q.tqoff, &Q.tsep, &Q.teven}) if (!rc) rc = BatchWs::ensure(*b, ntiles * 8);
+  if (!rc) rc = BatchWs::ensure(Q.base.flags, 2 * sizeof(Flags));
+  if (!rc) rc = BatchWs::ensure(W.tflag, ntiles * 4);
+  if (!rc) rc = BatchWs::ensure(W.info, 4);
+  if (rc) return rc;
+  const uint32_t spat = 0x01010101u * sep, qpat = 0x01010101u * (uint8_t)(quote < 0 ? 0 : quote), epat = 0x01010101u * escape;
+  const uint32_t qkeep = quote < 0 ? 0u : 0xFFFF0000u, x = state_in >> 1, parity_in = state_in & 1u;
+  auto U = [](BatchWs::Buf& b) { return (unsigned long long*)b.p; };
+  auto C = [](BatchWs::Buf& b) { return (const unsigned long long*)b.p; };
+  Flags* fl = (Flags*)Q.base.flags.p;
+  uint32_t* tflag = (uint32_t*)W.tflag.p;
+  hipLaunchKernelGGL(k_recount, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, qpat, qkeep, epat, x, U(Q.tq), U(Q.tsep),
+                     U(Q.teven), tflag);
+  hipLaunchKernelGGL(k_rescan, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, lo == 0 ? x : 0u, tflag, U(Q.tq));
+  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, C(Q.tq), U(Q.tqoff), fl);
+  hipLaunchKernelGGL(k_reselect, dim3((uint32_t)((ntiles + 255) / 256)), dim3(256), 0, sm, (uint32_t)ntiles, (const uint32_t*)tflag, C(Q.tq),
+                     C(Q.tqoff), C(Q.tsep), C(Q.teven), parity_in, U(Q.base.tcount), (uint32_t*)W.info.p);
+  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, C(Q.base.tcount), U(Q.base.toff), fl + 1);
+  HIPCHECK(hipGetLastError());
+  unsigned long long total = 0;
+  uint32_t info = 0;
+  HIPCHECK(hipMemcpyAsync(&total, &fl[1].total_len, 8, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipMemcpyAsync(&info, W.info.p, 4, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipStreamSynchronize(sm));
+  *state_out = (info >> 1) & 3u;
+  const int tail = !(info & 1u);   // (an escaped separator, or one inside quotes, as the last byte ends no record)
+  *nsep = total;
+  *nrec = total + (uint64_t)tail;
+  if (cap < *nrec + 1 || !d_off) return setErr(KX_E_CAPACITY, "kx_split_records_escaped: offsets buffer too small");
+  hipLaunchKernelGGL(k_rewrite, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, qpat, qkeep, epat, x, (const uint32_t*)tflag,
+                     C(Q.tqoff), parity_in, C(Q.base.toff), (unsigned long long)base, total, tail, (unsigned long long*)d_off);
+  HIPCHECK(hipGetLastError());
+  HIPCHECK(hipStreamSynchronize(sm));
+  return 0;
+}
+
+// the compute step of kx_run_records_fd, kx_run_records_fd_quoted and kx_run_records_fd_escaped
 struct RecordsRun {
   kx_program* p = nullptr;
   FdStream* fs = nullptr;
   uint8_t sep = '\n';
   int quote = -1;                                      // the quote byte, -1: none (kx_run_records_fd)
-  uint32_t parity = 0;                                 // quote parity at the start of the next window
+  int escape = -1;                                     // the escape byte, -1: none
+  uint32_t state = 0;                                  // at the start of the next window: bit 0 quote parity, bit 1 escaped
   RecQWs qws;
+  RecEWs ews;
   int report_fd = -1;
   RecWs ws;
   BatchWs::Buf off, ooff, docs, carry, one, longest;   // offsets; output offsets; doc records; the straddling record; its offsets
@@ -189,10 +252,12 @@ struct RecordsRun {
     uint64_t nrec = 0, nsep = 0;
     if (off.cap < 16) { int rc = BatchWs::ensure(off, (n / 32 + 2) * 8); if (rc) return rc; }
     if (timing) HIPCHECK(hipEventRecord(ev[0], nullptr));
-    uint32_t pout = parity;
+    uint32_t sout = state;
     auto split = [&] {
+      if (escape >= 0)
+        return splitRecordsEscaped(in, n, sep, quote, (uint8_t)escape, state, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, &sout, ews, nullptr);
       return quote < 0 ? splitRecords(in, n, sep, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, ws, nullptr)
-                       : splitRecordsQuoted(in, n, sep, (uint8_t)quote, parity, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, &pout, qws, nullptr);
+                       : splitRecordsQuoted(in, n, sep, (uint8_t)quote, state, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, &sout, qws, nullptr);
     };
     int rc = split();
     if (rc == KX_E_CAPACITY) {
@@ -200,7 +265,7 @@ struct RecordsRun {
       if (!rc) rc = split();
     }
     if (rc) return rc;
-    parity = pout;
+    state = sout;
     if (timing) { HIPCHECK(hipEventRecord(ev[1], nullptr)); HIPCHECK(hipEventSynchronize(ev[1])); st.split_ms += evMs(ev[0], ev[1]); }
     const uint64_t complete = last ? nrec : nsep;   // (a tail that is not the stream's end continues in the next window)
     const uint64_t* d_off = (const uint64_t*)off.p;
@@ -305,10 +370,31 @@ extern "C" int kx_split_records_quoted(const void* d_in, size_t n, uint8_t sep, 
   return rc;
 }
 
+extern "C" int kx_split_records_escaped(const void* d_in, size_t n, uint8_t sep, int quote, uint8_t escape, uint32_t state_in, uint64_t base,
+                                        uint64_t* d_off, uint64_t cap, uint64_t* n_records, uint32_t* state_out, void* stream) {
+  if (!n_records) return setErr(KX_E_ARG, "null argument");
+  *n_records = 0;
+  if (state_out) *state_out = 0;
+  if (quote < -1 || quote > 255) return setErr(KX_E_ARG, "kx_split_records_escaped: quote must be a byte value or -1");
+  if (quote == sep) return setErr(KX_E_ARG, "kx_split_records_escaped: the quote byte cannot be the separator");
+  if (escape == sep) return setErr(KX_E_ARG, "kx_split_records_escaped: the escape byte cannot be the separator");
+  if (quote == escape) return setErr(KX_E_ARG, "kx_split_records_escaped: the escape byte cannot be the quote byte");
+  if (state_in > 3 || (quote < 0 && (state_in & 1u))) return setErr(KX_E_ARG, "kx_split_records_escaped: state_in must be 0-3, bit 0 only with a quote");
+  if (n && !d_in) return setErr(KX_E_ARG, "kx_split_records_escaped: null input");
+  if (cap && !d_off) return setErr(KX_E_ARG, "kx_split_records_escaped: null offsets with a capacity");
+  RecEWs ws;
+  uint64_t nsep = 0;
+  uint32_t so = state_in;
+  const int rc = splitRecordsEscaped((const uint8_t*)d_in, n, sep, quote, escape, state_in, base, d_off, cap, n_records, &nsep, &so, ws,
+                                     (hipStream_t)stream);
+  if (state_out && (rc == 0 || rc == KX_E_CAPACITY)) *state_out = so;
+  return rc;
+}
+
 namespace {
 
-// kx_run_records_fd (quote < 0) and kx_run_records_fd_quoted
-int runRecordsFd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, int report_fd, kx_records_stats* stats) {
+// kx_run_records_fd (quote < 0, escape < 0), kx_run_records_fd_quoted (escape < 0) and kx_run_records_fd_escaped
+int runRecordsFd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, int escape, int report_fd, kx_records_stats* stats) {
   if (!p) return setErr(KX_E_ARG, "null argument");
   if (p->cfg.phase) return setErr(KX_E_ARG, "record mode runs every phase: kx_config::phase must be 0");
   const double t_begin = FdStream::nowMs();
@@ -321,7 +407,7 @@ int runRecordsFd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, i
   fsr.window = (window + fsr.CH - 1) / fsr.CH * fsr.CH;
   (void)hipGetDevice(&fsr.dev);
   RecordsRun R;
-  R.p = p; R.fs = &fsr; R.sep = sep; R.quote = quote; R.report_fd = report_fd;
+  R.p = p; R.fs = &fsr; R.sep = sep; R.quote = quote; R.escape = escape; R.report_fd = report_fd;
   R.timing = p->cfg.collect_timing != 0;
   int rc = 0;
   if (R.timing) for (auto& e : R.ev) if (hipEventCreate(&e) != hipSuccess) rc = setErr(KX_E_HIP, "hipEventCreate failed");
@@ -345,11 +431,20 @@ int runRecordsFd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, i
 }  // namespace
 
 extern "C" int kx_run_records_fd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int report_fd, kx_records_stats* stats) {
-  return runRecordsFd(p, in_fd, out_fd, sep, -1, report_fd, stats);
+  return runRecordsFd(p, in_fd, out_fd, sep, -1, -1, report_fd, stats);
 }
 
 extern "C" int kx_run_records_fd_quoted(kx_program* p, int in_fd, int out_fd, uint8_t sep, uint8_t quote, int report_fd,
                                         kx_records_stats* stats) {
   if (quote == sep) return setErr(KX_E_ARG, "kx_run_records_fd_quoted: the quote byte cannot be the separator");
-  return runRecordsFd(p, in_fd, out_fd, sep, quote, report_fd, stats);
+  return runRecordsFd(p, in_fd, out_fd, sep, quote, -1, report_fd, stats);
+}
+
+extern "C" int kx_run_records_fd_escaped(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, uint8_t escape, int report_fd,
+                                         kx_records_stats* stats) {
+  if (quote < -1 || quote > 255) return setErr(KX_E_ARG, "kx_run_records_fd_escaped: quote must be a byte value or -1");
+  if (quote == sep) return setErr(KX_E_ARG, "kx_run_records_fd_escaped: the quote byte cannot be the separator");
+  if (escape == sep) return setErr(KX_E_ARG, "kx_run_records_fd_escaped: the escape byte cannot be the separator");
+  if (quote == escape) return setErr(KX_E_ARG, "kx_run_records_fd_escaped: the escape byte cannot be the quote byte");
+  return runRecordsFd(p, in_fd, out_fd, sep, quote, escape, report_fd, stats);
 }

@@ -11,7 +11,9 @@
 // file on stdin over N GPUs (kx_run_fd_sharded).  `--records[=SEP]` (no counterpart either) runs every SEP-terminated record
 // (default a newline) as its own input (kx_run_records_fd): the accepted records' outputs go to stdout, one
 // "Match error at input symbol S in record R!" line per rejected record to stderr, and the run goes on to the end.  With
-// `--quote[=Q]` (default a double quote) a separator inside Q-quoted fields ends no record (kx_run_records_fd_quoted).
+// `--quote[=Q]` (default a double quote) a separator inside Q-quoted fields ends no record (kx_run_records_fd_quoted).  With
+// `--escape[=E]` (default a backslash) a byte after an unescaped E is only data: never a separator, a quote or an escape
+// (kx_run_records_fd_escaped, with or without --quote).
 //
 // BIN = this executable ++ KXP blob ++ libdir ++ trailer (see kexc main.cpp).
 // The engine is loaded with dlopen so that this file carries no HIP dependency.
@@ -69,9 +71,10 @@ static void usage(const char* name) {
   fprintf(stdout, "- \"%s -t\": runs normally, but prints timing to stderr.\n", name);
   fprintf(stdout, "- \"%s --records[=SEP]\": runs every line (or SEP-terminated record) as its own input; rejected ones are reported on stderr.\n", name);
   fprintf(stdout, "- \"%s --records[=SEP] --quote[=Q]\": the same, but a SEP inside Q-quoted fields (default Q: \") ends no record.\n", name);
+  fprintf(stdout, "- \"%s --records[=SEP] [--quote[=Q]] --escape[=E]\": the same, but a byte after an unescaped E (default E: \\) is only data.\n", name);
 }
 
-// --records=SEP, --quote=Q: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
+// --records=SEP, --quote=Q, --escape=E: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
 static bool parseSeparator(const char* a, uint8_t* sep) {
   auto hex = [](char c) { return c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1; };
   const size_t n = strlen(a);
@@ -111,9 +114,10 @@ int main(int argc, char** argv) {
   fclose(self);
 
   static struct option long_options[] = {{"phase", required_argument, 0, 'p'}, {"gpus", required_argument, 0, 'g'},
-                                         {"records", optional_argument, 0, 'r'}, {"quote", optional_argument, 0, 'q'}, {0, 0, 0, 0}};
-  bool timing = false, records = false, quoted = false;
-  uint8_t sep = '\n', quote = '"';
+                                         {"records", optional_argument, 0, 'r'}, {"quote", optional_argument, 0, 'q'},
+                                         {"escape", optional_argument, 0, 'e'}, {0, 0, 0, 0}};
+  bool timing = false, records = false, quoted = false, escaped = false;
+  uint8_t sep = '\n', quote = '"', escape = '\\';
   long phase = 0, gpus = 0;
   int c;
   while ((c = getopt_long(argc, argv, "ihtp:", long_options, nullptr)) != -1) {
@@ -137,6 +141,10 @@ int main(int argc, char** argv) {
         quoted = true;
         if (optarg && !parseSeparator(optarg, &quote)) { fprintf(stderr, "Invalid quote character: %s\n", optarg); return 1; }
         break;
+      case 'e':
+        escaped = true;
+        if (optarg && !parseSeparator(optarg, &escape)) { fprintf(stderr, "Invalid escape character: %s\n", optarg); return 1; }
+        break;
       case 'h':
       default: usage(argv[0]); return 1;
     }
@@ -146,6 +154,9 @@ int main(int argc, char** argv) {
   if (records && gpus) { fprintf(stderr, "%s: --records cannot be combined with --gpus\n", argv[0]); return 1; }
   if (quoted && !records) { fprintf(stderr, "%s: --quote needs --records\n", argv[0]); return 1; }
   if (quoted && quote == sep) { fprintf(stderr, "%s: the quote character cannot be the record separator\n", argv[0]); return 1; }
+  if (escaped && !records) { fprintf(stderr, "%s: --escape needs --records\n", argv[0]); return 1; }
+  if (escaped && escape == sep) { fprintf(stderr, "%s: the escape character cannot be the record separator\n", argv[0]); return 1; }
+  if (escaped && quoted && escape == quote) { fprintf(stderr, "%s: the escape character cannot be the quote character\n", argv[0]); return 1; }
   struct timeval t0, t1;
   if (timing) gettimeofday(&t0, nullptr);
 
@@ -165,10 +176,13 @@ int main(int argc, char** argv) {
     if (!runr) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd (--records needs a newer engine library)\n", argv[0]); return 1; }
     auto runq = (int (*)(kx_program*, int, int, uint8_t, uint8_t, int, kx_records_stats*))dlsym(h, "kx_run_records_fd_quoted");
     if (quoted && !runq) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_quoted (--quote needs a newer engine library)\n", argv[0]); return 1; }
+    auto rune = (int (*)(kx_program*, int, int, uint8_t, int, uint8_t, int, kx_records_stats*))dlsym(h, "kx_run_records_fd_escaped");
+    if (escaped && !rune) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_escaped (--escape needs a newer engine library)\n", argv[0]); return 1; }
     kx_program* prog = nullptr;
     if (load(blob.data(), blob.size(), &cfg, &prog)) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 1; }
     kx_records_stats rs;
-    rc = quoted ? runq(prog, STDIN_FILENO, STDOUT_FILENO, sep, quote, STDERR_FILENO, &rs) : runr(prog, STDIN_FILENO, STDOUT_FILENO, sep, STDERR_FILENO, &rs);
+    if (escaped) rc = rune(prog, STDIN_FILENO, STDOUT_FILENO, sep, quoted ? (int)quote : -1, escape, STDERR_FILENO, &rs);
+    else rc = quoted ? runq(prog, STDIN_FILENO, STDOUT_FILENO, sep, quote, STDERR_FILENO, &rs) : runr(prog, STDIN_FILENO, STDOUT_FILENO, sep, STDERR_FILENO, &rs);
     if (rc != 0 && rc != KX_MATCH_ERROR) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 1; }
     if (timing) {   // (a rejected record does not end the run: the time is printed either way)
       gettimeofday(&t1, nullptr);

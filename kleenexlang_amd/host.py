@@ -252,6 +252,63 @@ def split_records_model(data, sep=b"\n", quote=None, parity=0):
     return offs
 
 
+def _check_escape(escape, sep, quote=None):
+    """An escape character for the separator `sep` and the quote byte `quote` (None: none): one byte as _check_sep takes it, neither
+    the separator nor the quote → the int."""
+    e = _one_byte(escape, "escape character")
+    if e == _check_sep(sep):
+        raise ValueError("escape character: %r is also the record separator" % bytes([e]))
+    if quote is not None and e == _check_quote(quote, sep):
+        raise ValueError("escape character: %r is also the quote character" % bytes([e]))
+    return e
+
+
+def _check_state(state, quote):
+    """The state at a buffer's first byte of an escaped split: bit 0 the quote parity (only with a quote), bit 1 escaped."""
+    if isinstance(state, bool) or not isinstance(state, int):
+        raise TypeError("state: an int in 0-3, not %s" % type(state).__name__)
+    if not 0 <= state <= 3:
+        raise ValueError("state: 0-3, not %d" % state)
+    if quote is None and state & 1:
+        raise ValueError("state: bit 0 (the quote parity) needs a quote character")
+    return state
+
+
+def split_escaped_records_model(data, sep=b"\n", quote=None, escape=b"\\", state=0):
+    """kx_split_records_escaped in pure Python: (offsets, state_out).  An unescaped `escape` byte escapes the next byte; an
+    escaped byte is only data (never a separator, a quote or an escape).  With a `quote` byte a separator ends a record only at
+    even parity of the unescaped quotes before it.  state bit 0: the quote parity at data[0] (0 without a quote); bit 1: data[0]
+    is escaped.  state_out is the state after the last byte; a non-empty tail is a last record, as in split_records_model."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError("split_escaped_records_model: data must be bytes, not %s" % type(data).__name__)
+    s = _check_sep(sep)
+    q = None if quote is None else _check_quote(quote, sep)
+    e = _check_escape(escape, sep, quote)
+    _check_state(state, quote)
+    data = bytes(data)
+    import re
+    special = bytes([s, e]) if q is None else bytes([s, e, q])
+    p, x, offs, last = state & 1, state >> 1, [0], -1
+    for m in re.finditer(b"[" + b"".join(re.escape(bytes([c])) for c in special) + b"]", data):   # (only these bytes matter)
+        i, b = m.start(), data[m.start()]
+        if x and i != last + 1:
+            x = 0                           # (the escaped byte was some other byte)
+        last = i
+        if x:
+            x = 0                           # an escaped byte is only data
+        elif b == e:
+            x = 1
+        elif b == q:
+            p ^= 1
+        elif p == 0:
+            offs.append(i + 1)
+    if x and last != len(data) - 1:
+        x = 0
+    if offs[-1] != len(data):
+        offs.append(len(data))
+    return offs, p | x << 1
+
+
 def _check_values(values, what):
     import torch
     if not isinstance(values, torch.Tensor):
@@ -305,6 +362,33 @@ def split_quoted_records_tensor(values, sep=b"\n", quote=b'"', parity=0):
     if rc:
         raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
     return off, pout.value
+
+
+def split_escaped_records_tensor(values, sep=b"\n", quote=None, escape=b"\\", state=0):
+    """kx_split_records_escaped: split_records_tensor where an escaped byte is only data and, with a `quote` byte, a separator
+    inside quotes ends no record (split_escaped_records_model).  `state` is the state at values[0] (bit 0 quote parity, bit 1
+    escaped).  Returns (offsets, state after the last byte)."""
+    _check_values(values, "split_escaped_records_tensor")
+    s = _check_sep(sep)
+    q = -1 if quote is None else _check_quote(quote, sep)
+    e = _check_escape(escape, sep, quote)
+    st = _check_state(state, quote)
+    import torch
+    if not values.is_cuda:
+        raise EngineError("split_escaped_records_tensor: values must be on a HIP device (there is no CPU fallback)")
+    lib = load_engine()
+    stream = ctypes.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)
+    vptr = ctypes.c_void_p(values.data_ptr() if values.numel() else None)
+    n, sout = ctypes.c_uint64(), ctypes.c_uint32()
+    rc = lib.kx_split_records_escaped(vptr, values.numel(), s, q, e, st, 0, None, 0, ctypes.byref(n), ctypes.byref(sout), stream)
+    if rc not in (0, -3):
+        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
+    off = torch.empty(n.value + 1, dtype=torch.int64, device=values.device)
+    rc = lib.kx_split_records_escaped(vptr, values.numel(), s, q, e, st, 0, ctypes.c_void_p(off.data_ptr()), off.numel(), ctypes.byref(n),
+                                      ctypes.byref(sout), stream)
+    if rc:
+        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
+    return off, sout.value
 
 
 class KxDfInfo(ctypes.Structure):
@@ -398,6 +482,10 @@ def load_engine():
                                                 ctypes.POINTER(u32), vp]
         lib.kx_run_records_fd_quoted.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_int,
                                                  ctypes.POINTER(KxRecordsStats)]
+        lib.kx_split_records_escaped.argtypes = [vp, sz, ctypes.c_uint8, ctypes.c_int, ctypes.c_uint8, u32, u64, vp, u64,
+                                                 ctypes.POINTER(u64), ctypes.POINTER(u32), vp]
+        lib.kx_run_records_fd_escaped.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint8, ctypes.c_int, ctypes.c_uint8,
+                                                  ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
         lib.kx_shard_begin.argtypes = [vp, u32, vp, sz, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(vp)]
         lib.kx_shard_forward.argtypes = [vp, ctypes.POINTER(KxFwdSummary)]
         lib.kx_shard_fix_head.argtypes = [vp, u32, ctypes.POINTER(KxFwdSummary)]
@@ -879,37 +967,47 @@ class Program:
             res.append(MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]])
         return res
 
-    def run_records(self, data, sep=b"\n", device=None, quote=None):
+    def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None):
         """Record mode on bytes: every record of `data` (split after each `sep` byte, kx_split_records on the device) is a
         whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage).  With a `quote` byte
-        a separator inside quotes ends no record (kx_split_records_quoted from parity 0)."""
+        a separator inside quotes ends no record (kx_split_records_quoted from parity 0).  With an `escape` byte an escaped
+        byte is only data (kx_split_records_escaped from state 0)."""
         if not isinstance(data, (bytes, bytearray, memoryview)):
             raise TypeError("run_records: data must be bytes, not %s" % type(data).__name__)
         _check_sep(sep)
         if quote is not None:
             _check_quote(quote, sep)
+        if escape is not None:
+            _check_escape(escape, sep, quote)
         import torch
         data = bytes(data)
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         v = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else torch.empty(0, dtype=torch.uint8, device=dev)
-        offs = split_records_tensor(v, sep) if quote is None else split_quoted_records_tensor(v, sep, quote)[0]
+        if escape is not None:
+            offs = split_escaped_records_tensor(v, sep, quote, escape)[0]
+        else:
+            offs = split_records_tensor(v, sep) if quote is None else split_quoted_records_tensor(v, sep, quote)[0]
         out, ooff, status, fpos, fstage = self.run_batch_tensor(v, offs)
         torch.cuda.synchronize(dev)
         ob = out.cpu().numpy().tobytes()
         ooff, status, fpos, fstage = ooff.tolist(), status.tolist(), fpos.tolist(), fstage.tolist()
         return [MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]] for i in range(len(status))]
 
-    def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None):
+    def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None):
         """kx_run_records_fd: the stream on in_fd in record mode, outputs to out_fd, one line per rejected record to report_fd
         (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected.  With a `quote`
-        byte, kx_run_records_fd_quoted: a separator inside quotes ends no record."""
+        byte, kx_run_records_fd_quoted: a separator inside quotes ends no record.  With an `escape` byte,
+        kx_run_records_fd_escaped: an escaped byte is only data (with or without a quote)."""
         for name, fd in (("in_fd", in_fd), ("out_fd", out_fd), ("report_fd", report_fd)):
             if isinstance(fd, bool) or not isinstance(fd, int):
                 raise TypeError("run_records_fd: %s must be an int file descriptor, not %s" % (name, type(fd).__name__))
         s = _check_sep(sep)
         q = None if quote is None else _check_quote(quote, sep)
+        e = None if escape is None else _check_escape(escape, sep, quote)
         st = KxRecordsStats()
-        if q is None:
+        if e is not None:
+            rc = self._lib.kx_run_records_fd_escaped(self._h, in_fd, out_fd, s, -1 if q is None else q, e, report_fd, ctypes.byref(st))
+        elif q is None:
             rc = self._lib.kx_run_records_fd(self._h, in_fd, out_fd, s, report_fd, ctypes.byref(st))
         else:
             rc = self._lib.kx_run_records_fd_quoted(self._h, in_fd, out_fd, s, q, report_fd, ctypes.byref(st))

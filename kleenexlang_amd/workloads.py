@@ -10,6 +10,9 @@ Shapes follow the reference's own data:
   digits       BASELINE config 1: random ASCII digits, optionally newline-terminated
   rfc4180      RFC 4180 rows with quoted commas, "", quoted LF / CRLF line breaks and LF / CRLF row ends (no program of
                programs/ reads it: examples/csv_rfc4180.kex with quote-aware record mode)
+  csv_escaped  rows written by csv.writer(escapechar='\\', doublequote=False), QUOTE_MINIMAL and QUOTE_NONE, LF / CRLF row
+               ends; fields with '"', '\\', ',', LF, CR and empty ones (examples/csv_escaped.kex with `--records --quote --escape`)
+  tsv_escaped  MySQL-style TAB-separated rows: no quotes, '\\' before a literal TAB, LF or '\\' (`--records --escape`)
 Large inputs are a seeded base chunk replicated (the reference's own method for its big log,
 test/data/apache_log/generate_big_log.sh:4-5); `tiled_expected` states what the output of a
 replicated input must be in terms of the base chunk's output, which lets full-size runs be
@@ -98,7 +101,47 @@ def rfc4180_row(r):
     return ",".join(fields) + r.choice(["\n", "\n", "\n", "\r\n"])
 
 
-_LINE = {"apache_log": apache_log_line, "csv": csv_row, "datetime": datetime_line, "numbers": numbers_line, "rfc4180": rfc4180_row}
+_ESCCH = _FIELDCH + "\"\\,'"
+
+
+def csv_escaped_row(r):
+    """One row of csv.writer(escapechar='\\', doublequote=False) for escape-aware record mode (examples/csv_escaped.kex):
+    QUOTE_MINIMAL or QUOTE_NONE, LF or CRLF row end, 1-8 fields (maybe empty) that may hold '"', '\\', ',' and, in about 10 % of
+    the rows, an LF or a CR.  A CR goes only into CRLF rows: a writer whose line ends are LF neither quotes nor escapes a bare CR
+    in a field, and csv.reader would end the row there.  QUOTE_NONE refuses a row of one empty field: such a row gets a letter."""
+    import csv
+    import io
+    quoting = r.choice([csv.QUOTE_MINIMAL, csv.QUOTE_NONE])
+    end = r.choice(["\n", "\n", "\r\n"])
+    breaks = ["\n", "\r", "\r\n"] if end == "\r\n" else ["\n"]
+    fields = []
+    for _ in range(r.randint(1, 8)):
+        u = r.random()
+        fields.append("" if u < 0.15 else _word(r, 1, 14, _FIELDCH) if u < 0.5 else _word(r, 1, 16, _ESCCH))
+    if r.random() < 0.1:   # a line break inside one field
+        k = r.randrange(len(fields))
+        fields[k] += r.choice(breaks) + _word(r, 0, 8, _ESCCH)
+    if quoting == csv.QUOTE_NONE and fields == [""]:
+        fields = ["x"]
+    b = io.StringIO()
+    csv.writer(b, escapechar="\\", doublequote=False, quoting=quoting, lineterminator=end).writerow(fields)
+    return b.getvalue()
+
+
+def tsv_escaped_row(r):
+    """One MySQL `SELECT ... INTO OUTFILE`-style row: TAB-separated fields with no quoting, a '\\' before every literal TAB, LF or
+    '\\' in a field (about 10 % of the rows hold an escaped LF or TAB), LF row end."""
+    fields = []
+    for _ in range(r.randint(1, 8)):
+        f = "" if r.random() < 0.1 else _word(r, 1, 14, _FIELDCH + "\"\\,'")
+        if r.random() < 0.03:
+            f += r.choice(["\n", "\t"]) + _word(r, 0, 8, _FIELDCH)
+        fields.append(f.replace("\\", "\\\\").replace("\t", "\\\t").replace("\n", "\\\n"))
+    return "\t".join(fields) + "\n"
+
+
+_LINE = {"apache_log": apache_log_line, "csv": csv_row, "datetime": datetime_line, "numbers": numbers_line, "rfc4180": rfc4180_row,
+         "csv_escaped": csv_escaped_row, "tsv_escaped": tsv_escaped_row}
 # which input shape each workload program consumes
 PROGRAM_INPUT = {"apache_log": "apache_log", "csv2json": "csv", "iso_datetime_to_json": "datetime",
                  "thousand_sep": "numbers"}
