@@ -98,6 +98,8 @@ typedef struct kx_config {
   uint32_t act_lanes;      /* one lane per chunk (token-dense streams): 0 auto, 1 off, 2 on                           [KX_ACT_LANES] */
   uint32_t act_chunk;      /* wanted chunk bytes: 0 auto (2048 / 4096)                                                 [KX_ACT_CHUNK] */
   /* ---- batched runs (run time) ---- */
+  uint32_t batch_actions;  /* kx_run_batch, stages with register actions: 0 / 1 = every document takes the single-document route,
+                              2 = the batch replay (k_bact_*: one lane or one wave per document)          [KX_BATCH_ACTIONS=0 / 1] */
   uint32_t batch_doc_max;  /* kx_run_batch: longest document the batch kernels take; longer ones go through the single-document
                               route: 0 = 64 KiB                                                                                */
   uint32_t reserved[3];    /* must be 0 */
@@ -204,10 +206,13 @@ int kx_run_fd(kx_program* prog, int in_fd, int out_fd, kx_stats* stats);
  *   KX_E_CAPACITY  *out_len = the bytes needed; d_out_off and d_docs are filled.  d_out = NULL, cap = 0 is the size query.
  *   KX_E_ARG  among others: the offsets decrease somewhere (checked on the device before anything reads a document)
  *   < 0  other errors, as elsewhere (kx_last_error)
- * The batch kernels take documents of at most kx_config::batch_doc_max bytes, one lane per document.  Longer documents, and
- * EVERY document of a stage with register actions (whose replay is sequential, kx_stage_has_actions), go through the
- * single-document driver one at a time: correct, but not fast for many small documents of such a stage (stats->docs_routed
- * counts them).  A call leaves kx_stage_delayed_form of every stage as it found it. */
+ * The batch kernels take documents of at most kx_config::batch_doc_max bytes, one lane per document.  Longer documents go
+ * through the single-document driver one at a time (stats->docs_routed counts them).  A stage with register actions
+ * (kx_stage_has_actions) emits a token stream per document, which has to be replayed: with kx_config::batch_actions = 2 the
+ * batch kernels do it, one lane or one wave per document (stats->docs_replayed), and only a document longer than
+ * batch_doc_max, or one whose replay outgrows its per-document arena, takes the route.  With batch_actions = 0 or 1 (the
+ * library's default) EVERY document of such a stage takes the route: correct, but ~0.35 ms per document.  A call leaves
+ * kx_stage_delayed_form of every stage as it found it. */
 typedef struct kx_batch_doc {
   uint64_t fail_pos;
   uint32_t status;      /* 0 accepted, 1 match error */
@@ -218,7 +223,9 @@ typedef struct kx_batch_stats {
   uint64_t docs_routed;    /* document runs that took the single-document route, summed over the stages */
   uint64_t in_bytes, out_bytes;
   float forward_ms, back_ms, scan_ms, emit_ms, routed_ms, total_ms;   /* HIP events, with kx_config::collect_timing; summed over the stages */
-  uint32_t reserved[4];
+  uint64_t docs_replayed;  /* document runs of action stages replayed by the batch kernels (kx_config::batch_actions = 2), summed over the stages */
+  float actions_ms;        /* the batch replay: measure + both replay kernels (HIP events, as above) */
+  uint32_t reserved[1];
 } kx_batch_stats;
 int kx_run_batch(kx_program* prog, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, void* d_out, size_t cap,
                  uint64_t* d_out_off, kx_batch_doc* d_docs, size_t* out_len, kx_batch_stats* stats, void* stream);
@@ -241,7 +248,8 @@ typedef struct kx_records_stats {
    "Match error at input symbol S in record R!" per rejected record to report_fd (-1: none), S the record's own fail_pos,
    R counted from 1.  Returns 0 (every record accepted), KX_MATCH_ERROR (some rejected; the rest is written in full) or an
    error.  Windows as kx_run_fd (kx_config::window_bytes, KX_WINDOW_BYTES); kx_config::phase must be 0.  Records of a stage
-   with register actions take kx_run_batch's single-document route (records_routed): correct, not fast. */
+   with register actions are replayed by kx_run_batch's batch kernels where kx_config::batch_actions = 2 (the produced binary
+   sets it for --records); otherwise each takes the single-document route (records_routed): correct, not fast. */
 int kx_run_records_fd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int report_fd, kx_records_stats* stats);
 
 /* ---- quote-aware record mode: a separator inside quotes ends no record ----------------------------------------------------

@@ -280,7 +280,8 @@ __global__ void k_bplace(const BRoute* __restrict__ res, const uint8_t* __restri
 struct BatchWs {
   struct Buf { void* p = nullptr; size_t cap = 0; };
   Buf chk, brec, docs, routes, ctr, flags, wsum, woff, vals[2], offs[2], rin, rout, tok, tokout, rres;
-  hipEvent_t ev[8] = {};
+  Buf actr, atok, atoff, atab, awlist, adeep, aretry, astates, ascr, aheap;   // the batch replay of action stages (kx_batch_actions.inc)
+  hipEvent_t ev[10] = {};
   bool have_events = false, lds_set = false;
   static int ensure(Buf& b, size_t bytes) {   // contents are not kept
     if (b.cap >= bytes) return 0;
@@ -302,7 +303,8 @@ struct BatchWs {
     return 0;
   }
   ~BatchWs() {
-    for (Buf* b : {&chk, &brec, &docs, &routes, &ctr, &flags, &wsum, &woff, &vals[0], &vals[1], &offs[0], &offs[1], &rin, &rout, &tok, &tokout, &rres})
+    for (Buf* b : {&chk, &brec, &docs, &routes, &ctr, &flags, &wsum, &woff, &vals[0], &vals[1], &offs[0], &offs[1], &rin, &rout, &tok, &tokout, &rres,
+                   &actr, &atok, &atoff, &atab, &awlist, &adeep, &aretry, &astates, &ascr, &aheap})
       if (b->p) (void)hipFree(b->p);
     if (have_events) for (auto& e : ev) (void)hipEventDestroy(e);
   }

@@ -5,6 +5,11 @@
 // k_bback → scan of the document lengths → k_binit + k_bemit (lane = piece) + k_bplace.  Stage s + 1's batch is stage s's
 // output batch (values + offsets); a document rejected at stage s is skipped by the later stages.  Three host round trips per
 // stage (routed count, total length, end) plus one for the offset check: the call's fixed cost, whatever the number of documents.
+//
+// A stage with register actions, kx_config::batch_actions = 2 (kx_batch_actions.inc): the steps above place the documents' TOKEN
+// STREAMS in a workspace batch; k_bact_measure → the scan again, now over the replayed lengths → k_bact_lanes + k_bact_waves
+// write every document's replayed bytes to their final place.  One more round trip (the replayed total and the class counts).
+// With batch_actions = 0 / 1 every document of such a stage goes through batchRouteOne.
 
 namespace {
 
@@ -59,6 +64,128 @@ int batchRouteOne(kx_program* p, uint32_t st, const uint8_t* d_doc, uint64_t n, 
     HIPCHECK(hipGetLastError());
   }
   r.start = pos; r.len = al; pos += al;
+  return 0;
+}
+
+// The batch replay of an action stage (kx_batch_actions.inc): `tok` / `toff` hold the documents' token streams (tok_total bytes),
+// W.docs their records.  Measures, scans the replayed lengths into stage_off, and replays every document to its final place:
+// the caller's d_out for the last stage, else the stage's workspace batch.  *dst_out / *total_out: where the replayed batch is.
+int batchReplay(kx_program* p, uint32_t st, bool last, uint64_t nd, const uint8_t* cur, const unsigned long long* cur_off, const uint8_t* tok,
+                const unsigned long long* toff, unsigned long long tok_total, unsigned long long* stage_off, void* d_out, size_t cap, size_t* out_len,
+                unsigned long long nr, hipStream_t sm, BatchWs& W, kx_batch_stats& bst, uint8_t** dst_out, unsigned long long* total_out) {
+  Stage& S = p->stages[st];
+  const bool timing = p->cfg.collect_timing != 0;
+  const uint32_t nregs = S.act_regs;
+  const bool small = nregs <= 32;   // (registers the chunk instance of actions_body keeps in LDS)
+  const uint32_t mgrid = (uint32_t)std::min<uint64_t>((nd + BACT_MT - 1) / BACT_MT, (uint64_t)p->ncu * 4);
+  const uint32_t wgrid_max = (uint32_t)p->ncu * (small ? 32u : 2u);
+  const size_t tab_words = (size_t)mgrid * BACT_MT * (BACT_TAB_FRAMES + (nregs > LANE_REGS ? nregs - LANE_REGS : 0));
+  int rc = BatchWs::ensure(W.actr, BA_N * 8);
+  if (!rc) rc = BatchWs::ensure(W.atab, tab_words * 4);
+  if (!rc) rc = BatchWs::ensure(W.awlist, nd * 4);
+  if (!rc) rc = BatchWs::ensure(W.adeep, nd * 4);
+  if (!rc) rc = BatchWs::ensure(W.aretry, nd * 4);
+  if (rc) return rc;
+  unsigned long long* actr = (unsigned long long*)W.actr.p;
+  BDoc* docs = (BDoc*)W.docs.p;
+  HIPCHECK(hipMemsetAsync(actr, 0, BA_N * 8, sm));
+  if (timing) HIPCHECK(hipEventRecord(W.ev[8], sm));
+  hipLaunchKernelGGL(k_bact_measure, dim3(mgrid), dim3(BACT_MT), 0, sm, tok, toff, (unsigned long long)nd, nregs, p->cfg.act_lanes, docs,
+                     (uint32_t*)W.atab.p, (uint32_t*)W.awlist.p, (uint32_t*)W.adeep.p, actr);
+  const uint32_t ng = (uint32_t)((nd + 1023) / 1024), g1024 = (uint32_t)((nd + 1 + 1023) / 1024);
+  hipLaunchKernelGGL(k_bscan_reduce, dim3(ng), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (unsigned long long*)W.wsum.p);
+  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, ng, (const unsigned long long*)W.wsum.p, (unsigned long long*)W.woff.p, (Flags*)W.flags.p);
+  hipLaunchKernelGGL(k_bscan_down, dim3(g1024), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (const unsigned long long*)W.woff.p,
+                     (const Flags*)W.flags.p, stage_off);
+  HIPCHECK(hipGetLastError());
+  unsigned long long hc[BA_N] = {}, total = 0;
+  HIPCHECK(hipMemcpyAsync(hc, actr, sizeof hc, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipMemcpyAsync(&total, &((Flags*)W.flags.p)->total_len, 8, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipStreamSynchronize(sm));
+  std::vector<uint32_t> ids;
+  std::vector<BRoute> routes;
+  // the route for the listed documents (`ids`, device list `d_ids`): results in `routes`, their outputs in W.rout from `rpos` on
+  size_t rpos = 0;
+  auto routeListed = [&](const void* d_ids, unsigned long long n_ids) -> int {
+    ids.resize(n_ids);
+    HIPCHECK(hipMemcpyAsync(ids.data(), d_ids, n_ids * 4, hipMemcpyDeviceToHost, sm));
+    HIPCHECK(hipStreamSynchronize(sm));
+    std::sort(ids.begin(), ids.end());
+    routes.clear();
+    for (uint32_t i : ids) {
+      unsigned long long se[2];
+      HIPCHECK(hipMemcpyAsync(se, cur_off + i, 16, hipMemcpyDeviceToHost, sm));
+      HIPCHECK(hipStreamSynchronize(sm));
+      BRoute r{se[0], se[1] - se[0], i, 0, 0};
+      int e = batchRouteOne(p, st, cur + r.start, r.len, sm, W, rpos, r);
+      if (e) return e;
+      routes.push_back(r);
+    }
+    return 0;
+  };
+  if (hc[BA_DEEP]) {   // nested deeper than the replay's 64 frames: the route reports it, as for the document alone
+    rc = routeListed(W.adeep.p, hc[BA_DEEP]);
+    return rc ? rc : setErr(KX_E_ARG, "register redirections nested deeper than 64");
+  }
+  uint8_t* dst = nullptr;
+  if (last) {
+    *out_len = total;
+    bst.out_bytes = total;
+    if (total > cap || (total && !d_out)) return setErr(KX_E_CAPACITY, "output buffer too small");
+    dst = (uint8_t*)d_out;
+  } else {
+    rc = BatchWs::ensure(W.vals[st & 1], total + 16);
+    if (rc) return rc;
+    dst = (uint8_t*)W.vals[st & 1].p;
+  }
+  const unsigned long long nw = hc[BA_WAVES];
+  if (total) {
+    // the documents' stretches of the two arenas (frames: n + 64, registers: 2 n + 1024 bytes each, as k_actions_lanes sizes them)
+    rc = BatchWs::ensure(W.ascr, tok_total + 64 * (size_t)nd + 64);
+    if (!rc) rc = BatchWs::ensure(W.aheap, 2 * tok_total + 1024 * (size_t)nd + 1024);
+    if (rc) return rc;
+    if (hc[BA_REPLAY] > nw)
+      hipLaunchKernelGGL(k_bact_lanes, dim3(mgrid), dim3(BACT_MT), 0, sm, tok, toff, (unsigned long long)nd, nregs, (const BDoc*)docs,
+                         (const unsigned long long*)stage_off, (uint8_t*)W.ascr.p, (uint8_t*)W.aheap.p, dst, (uint32_t*)W.aretry.p, actr);
+    if (nw) {
+      const uint32_t wgrid = (uint32_t)std::min<unsigned long long>(nw, wgrid_max);
+      rc = BatchWs::ensure(W.astates, (size_t)wgrid * sizeof(ActState));
+      if (rc) return rc;
+      auto* const wave_kernel = small ? &k_bact_waves<1024, 32> : &k_bact_waves<16384, 256>;   // (the chunk instance / the streaming instance of actions_body)
+      hipLaunchKernelGGL(wave_kernel, dim3(wgrid), dim3(64), 0, sm, tok, toff, nregs, (const BDoc*)docs,
+                         (const unsigned long long*)stage_off, (const uint32_t*)W.awlist.p, (ActState*)W.astates.p, (uint8_t*)W.ascr.p,
+                         (uint8_t*)W.aheap.p, dst, (uint32_t*)W.aretry.p, actr);
+    }
+    // the documents routed for their length hold their replayed output already
+    if (nr) hipLaunchKernelGGL(k_bplace, dim3((uint32_t)nr), dim3(256), 0, sm, (const BRoute*)W.rres.p, (const uint8_t*)W.rout.p, (const unsigned long long*)stage_off, dst);
+  }
+  if (timing) HIPCHECK(hipEventRecord(W.ev[9], sm));
+  HIPCHECK(hipGetLastError());
+  unsigned long long nretry = 0;
+  HIPCHECK(hipMemcpyAsync(&nretry, actr + BA_RETRY, 8, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipStreamSynchronize(sm));
+  if (timing) bst.actions_ms += evMs(W.ev[8], W.ev[9]);
+  if (nretry) {   // a replay outgrew its document's arena: the route, to the same place (the measured length holds)
+    const auto rt0 = std::chrono::steady_clock::now();
+    rpos = 0;     // (the long documents' outputs have been placed)
+    rc = routeListed(W.aretry.p, nretry);
+    if (rc) return rc;
+    std::vector<BDoc> hd(1);
+    for (const BRoute& r : routes) {
+      HIPCHECK(hipMemcpy(hd.data(), docs + r.doc, sizeof(BDoc), hipMemcpyDeviceToHost));
+      if (r.rejected || r.len != hd[0].len) return setErr(KX_E_HIP, "kx_run_batch: the batch replay measured a length the single-document route does not give");
+    }
+    rc = BatchWs::ensure(W.rres, nretry * sizeof(BRoute));
+    if (rc) return rc;
+    HIPCHECK(hipMemcpyAsync(W.rres.p, routes.data(), nretry * sizeof(BRoute), hipMemcpyHostToDevice, sm));
+    hipLaunchKernelGGL(k_bplace, dim3((uint32_t)nretry), dim3(256), 0, sm, (const BRoute*)W.rres.p, (const uint8_t*)W.rout.p, (const unsigned long long*)stage_off, dst);
+    HIPCHECK(hipGetLastError());
+    HIPCHECK(hipStreamSynchronize(sm));
+    bst.docs_routed += nretry;
+    bst.routed_ms += (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - rt0).count();
+  }
+  bst.docs_replayed += hc[BA_REPLAY] - nretry;
+  *dst_out = dst; *total_out = total;
   return 0;
 }
 
@@ -147,6 +274,7 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
     Stage& S = p->stages[st];
     const bool last = st + 1 == ns;
     const bool wide = S.general;
+    const bool replay = S.act && p->cfg.batch_actions == 2;   // the batch replay; else every document of an action stage is routed
     const size_t lds = S.lds_bytes;
     const uint64_t nchk = (cur_bytes >> 5) + nd + 2, nslots = (cur_bytes >> 6) + nd;   // (k_bback writes every piece slot below nslots)
     rc = BatchWs::ensure(W.chk, nchk * 2);
@@ -154,12 +282,14 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
     if (rc) break;
     unsigned long long* out_off = last ? (unsigned long long*)d_out_off : nullptr;
     if (!last) { rc = BatchWs::ensure(W.offs[st & 1], (nd + 1) * 8); if (rc) break; out_off = (unsigned long long*)W.offs[st & 1].p; }
+    unsigned long long* const stage_off = out_off;   // (where the stage's output offsets go)
+    if (replay) { rc = BatchWs::ensure(W.atoff, (nd + 1) * 8); if (rc) break; out_off = (unsigned long long*)W.atoff.p; }   // first the token streams'
     BDoc* docs = (BDoc*)W.docs.p; BRec* brec = (BRec*)W.brec.p; uint16_t* chk = (uint16_t*)W.chk.p;
     // forward: lane = document
     HIPCHECK(hipMemsetAsync(ctr + BC_ROUTED, 0, 8, sm));
     if (timing) HIPCHECK(hipEventRecord(W.ev[0], sm));
     hipLaunchKernelGGL(wide ? k_bforward<true> : k_bforward<false>, dim3(bgrid), dim3(BATCH_BT), lds, sm, cur, cur_off, (unsigned long long)nd,
-                       (unsigned long long)doc_max, S.act ? 1 : 0, st, (BDoc*)W.docs.p, d_docs, chk, (BRoute*)W.routes.p, ctr, S.T);
+                       (unsigned long long)doc_max, S.act && !replay ? 1 : 0, st, (BDoc*)W.docs.p, d_docs, chk, (BRoute*)W.routes.p, ctr, S.T);
     if (timing) HIPCHECK(hipEventRecord(W.ev[1], sm));
     HIPCHECK(hipGetLastError());
     unsigned long long nr = 0;
@@ -193,13 +323,16 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
       HIPCHECK(hipStreamSynchronize(sm));
       bst.routed_ms += (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - rt0).count();
     }
-    // exclusive scan of the document lengths into out_off (out_off[nd] = the stage's total)
-    if (timing) HIPCHECK(hipEventRecord(W.ev[4], sm));
+    // exclusive scan of the document lengths into `off` (off[nd] = the total, also left in Flags::total_len)
     const uint32_t ng = (uint32_t)((nd + 1023) / 1024);
-    hipLaunchKernelGGL(k_bscan_reduce, dim3(ng), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (unsigned long long*)W.wsum.p);
-    hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, ng, (const unsigned long long*)W.wsum.p, (unsigned long long*)W.woff.p, (Flags*)W.flags.p);
-    hipLaunchKernelGGL(k_bscan_down, dim3(g1024), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (const unsigned long long*)W.woff.p,
-                       (const Flags*)W.flags.p, out_off);
+    auto scanDocs = [&](unsigned long long* off) {
+      hipLaunchKernelGGL(k_bscan_reduce, dim3(ng), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (unsigned long long*)W.wsum.p);
+      hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, ng, (const unsigned long long*)W.wsum.p, (unsigned long long*)W.woff.p, (Flags*)W.flags.p);
+      hipLaunchKernelGGL(k_bscan_down, dim3(g1024), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (const unsigned long long*)W.woff.p,
+                         (const Flags*)W.flags.p, off);
+    };
+    if (timing) HIPCHECK(hipEventRecord(W.ev[4], sm));
+    scanDocs(out_off);
     if (timing) HIPCHECK(hipEventRecord(W.ev[5], sm));
     HIPCHECK(hipGetLastError());
     unsigned long long total = 0;
@@ -207,7 +340,11 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
     HIPCHECK(hipStreamSynchronize(sm));
     if (timing) { bst.back_ms += evMs(W.ev[2], W.ev[3]); bst.scan_ms += evMs(W.ev[4], W.ev[5]); }
     uint8_t* dst = nullptr;
-    if (last) {
+    if (replay) {   // (the token streams: a workspace batch, whatever the stage's position)
+      rc = BatchWs::ensure(W.atok, total + 16);
+      if (rc) break;
+      dst = (uint8_t*)W.atok.p;
+    } else if (last) {
       *out_len = total;
       bst.out_bytes = total;
       if (total > cap || (total && !d_out)) { rc = setErr(KX_E_CAPACITY, "output buffer too small"); break; }
@@ -224,12 +361,18 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
       const uint64_t eg = (nslots + BATCH_BT - 1) / BATCH_BT;
       hipLaunchKernelGGL(wide ? k_bemit<true> : k_bemit<false>, dim3((uint32_t)(eg < bgrid ? eg : bgrid)), dim3(BATCH_BT), lds, sm, cur, cur_off,
                          (unsigned long long)nslots, (const BDoc*)docs, (const uint16_t*)chk, (const BRec*)brec, (const unsigned long long*)out_off, dst, S.T);
-      if (nr) hipLaunchKernelGGL(k_bplace, dim3((uint32_t)nr), dim3(256), 0, sm, (const BRoute*)W.rres.p, (const uint8_t*)W.rout.p, (const unsigned long long*)out_off, dst);
+      // (a replayed stage's routed documents hold their REPLAYED output: placed behind the replay, below)
+      if (nr && !replay) hipLaunchKernelGGL(k_bplace, dim3((uint32_t)nr), dim3(256), 0, sm, (const BRoute*)W.rres.p, (const uint8_t*)W.rout.p, (const unsigned long long*)out_off, dst);
     }
     if (timing) HIPCHECK(hipEventRecord(W.ev[7], sm));
     HIPCHECK(hipGetLastError());
+    if (replay) {
+      rc = batchReplay(p, st, last, nd, cur, cur_off, (const uint8_t*)dst, out_off, total, stage_off, d_out, cap, out_len, nr, sm, W, bst, &dst, &total);
+      if (rc) break;
+      out_off = stage_off;
+    }
     HIPCHECK(hipStreamSynchronize(sm));
-    if (timing) { bst.emit_ms += evMs(W.ev[6], W.ev[7]); bst.total_ms += evMs(W.ev[0], W.ev[7]); }
+    if (timing) { bst.emit_ms += evMs(W.ev[6], W.ev[7]); bst.total_ms += evMs(W.ev[0], replay ? W.ev[9] : W.ev[7]); }
     cur = dst; cur_off = out_off; cur_bytes = total;
   }
   if (rc == 0 || rc == KX_E_CAPACITY) {

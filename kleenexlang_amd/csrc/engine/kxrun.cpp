@@ -61,6 +61,7 @@ static kx_config configFromEnv() {
   c.act_prefix3_min = (uint32_t)num("KX_ACT_PREFIX3_MIN", 0);
   c.act_lanes = tri("KX_ACT_LANES");
   c.act_chunk = (uint32_t)num("KX_ACT_CHUNK", 0);
+  c.batch_actions = tri("KX_BATCH_ACTIONS");   // (0: every document of an action stage takes the route; else the batch replay)
   return c;
 }
 
@@ -178,6 +179,9 @@ int main(int argc, char** argv) {
     if (quoted && !runq) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_quoted (--quote needs a newer engine library)\n", argv[0]); return 1; }
     auto rune = (int (*)(kx_program*, int, int, uint8_t, int, uint8_t, int, kx_records_stats*))dlsym(h, "kx_run_records_fd_escaped");
     if (escaped && !rune) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_escaped (--escape needs a newer engine library)\n", argv[0]); return 1; }
+    // record mode is where the single-document route is unusable (a third of a millisecond per record): stages with register
+    // actions are replayed by the batch kernels unless KX_BATCH_ACTIONS=0 asks for the route
+    if (!cfg.batch_actions) cfg.batch_actions = 2;
     kx_program* prog = nullptr;
     if (load(blob.data(), blob.size(), &cfg, &prog)) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 1; }
     kx_records_stats rs;

@@ -6,6 +6,7 @@ binaries (``Match error at input symbol N!``, exit code 1 — Backends/C.hs:79-8
 There is no CPU fallback: if ``libkxhip.so`` is missing or no HIP device is
 present, constructing a :class:`Program` raises.
 """
+import contextlib
 import ctypes
 import os
 
@@ -67,7 +68,8 @@ class KxConfig(ctypes.Structure):
                 ("collect_timing", ctypes.c_uint32), ("phase", ctypes.c_uint32), ("window_bytes", ctypes.c_uint64)] + \
                [(k, ctypes.c_uint32) for k in ("delayed_form", "delay", "merge_window", "inline_consts", "job_stride", "disable", "force",
                                                "emit_waves", "emit_half", "emit_inplace", "emit_staging", "df_backoff", "debug_flags",
-                                               "act_par_min", "act_prefix3_min", "act_lanes", "act_chunk", "batch_doc_max")] + \
+                                               "act_par_min", "act_prefix3_min", "act_lanes", "act_chunk", "batch_actions",
+                                               "batch_doc_max")] + \
                [("reserved", ctypes.c_uint32 * 3)]
 
 
@@ -114,6 +116,7 @@ def config_from_env(env=None, **fields):
     c.act_prefix3_min = num("KX_ACT_PREFIX3_MIN")
     c.act_lanes = tri("KX_ACT_LANES")
     c.act_chunk = num("KX_ACT_CHUNK")
+    c.batch_actions = tri("KX_BATCH_ACTIONS")     # (0: every document of an action stage takes the route; else the batch replay)
     for k, v in fields.items():
         setattr(c, k, v)
     return c
@@ -128,7 +131,7 @@ class KxBatchStats(ctypes.Structure):
     """include/kxhip.h::kx_batch_stats."""
     _fields_ = [(k, ctypes.c_uint64) for k in ("docs", "docs_rejected", "docs_routed", "in_bytes", "out_bytes")] + \
                [(k, ctypes.c_float) for k in ("forward_ms", "back_ms", "scan_ms", "emit_ms", "routed_ms", "total_ms")] + \
-               [("reserved", ctypes.c_uint32 * 4)]
+               [("docs_replayed", ctypes.c_uint64), ("actions_ms", ctypes.c_float), ("reserved", ctypes.c_uint32 * 1)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
@@ -967,11 +970,30 @@ class Program:
             res.append(MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]])
         return res
 
-    def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None):
+    @contextlib.contextmanager
+    def _batch_actions_for_call(self, batch_actions):
+        """kx_config::batch_actions for one call of record mode, as the produced binary sets it for --records: True turns the
+        batch replay on unless the program's configuration says 1 (the route) explicitly; False asks for the route."""
+        old = self._cfg.batch_actions
+        new = (old or 2) if batch_actions else 1
+        if new != old:
+            self._cfg.batch_actions = new
+            if self._lib.kx_set_config(self._h, ctypes.byref(self._cfg)):
+                self._cfg.batch_actions = old
+                raise EngineError(self._err())
+        try:
+            yield
+        finally:
+            if new != old:
+                self._cfg.batch_actions = old
+                self._lib.kx_set_config(self._h, ctypes.byref(self._cfg))
+
+    def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None, batch_actions=True):
         """Record mode on bytes: every record of `data` (split after each `sep` byte, kx_split_records on the device) is a
         whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage).  With a `quote` byte
         a separator inside quotes ends no record (kx_split_records_quoted from parity 0).  With an `escape` byte an escaped
-        byte is only data (kx_split_records_escaped from state 0)."""
+        byte is only data (kx_split_records_escaped from state 0).  `batch_actions`: stages with register actions are replayed
+        by the batch kernels (kx_config::batch_actions = 2 for this call) instead of routing every record."""
         if not isinstance(data, (bytes, bytearray, memoryview)):
             raise TypeError("run_records: data must be bytes, not %s" % type(data).__name__)
         _check_sep(sep)
@@ -987,17 +1009,18 @@ class Program:
             offs = split_escaped_records_tensor(v, sep, quote, escape)[0]
         else:
             offs = split_records_tensor(v, sep) if quote is None else split_quoted_records_tensor(v, sep, quote)[0]
-        out, ooff, status, fpos, fstage = self.run_batch_tensor(v, offs)
+        with self._batch_actions_for_call(batch_actions):
+            out, ooff, status, fpos, fstage = self.run_batch_tensor(v, offs)
         torch.cuda.synchronize(dev)
         ob = out.cpu().numpy().tobytes()
         ooff, status, fpos, fstage = ooff.tolist(), status.tolist(), fpos.tolist(), fstage.tolist()
         return [MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]] for i in range(len(status))]
 
-    def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None):
+    def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None, batch_actions=True):
         """kx_run_records_fd: the stream on in_fd in record mode, outputs to out_fd, one line per rejected record to report_fd
         (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected.  With a `quote`
         byte, kx_run_records_fd_quoted: a separator inside quotes ends no record.  With an `escape` byte,
-        kx_run_records_fd_escaped: an escaped byte is only data (with or without a quote)."""
+        kx_run_records_fd_escaped: an escaped byte is only data (with or without a quote).  `batch_actions` as in run_records."""
         for name, fd in (("in_fd", in_fd), ("out_fd", out_fd), ("report_fd", report_fd)):
             if isinstance(fd, bool) or not isinstance(fd, int):
                 raise TypeError("run_records_fd: %s must be an int file descriptor, not %s" % (name, type(fd).__name__))
@@ -1005,12 +1028,13 @@ class Program:
         q = None if quote is None else _check_quote(quote, sep)
         e = None if escape is None else _check_escape(escape, sep, quote)
         st = KxRecordsStats()
-        if e is not None:
-            rc = self._lib.kx_run_records_fd_escaped(self._h, in_fd, out_fd, s, -1 if q is None else q, e, report_fd, ctypes.byref(st))
-        elif q is None:
-            rc = self._lib.kx_run_records_fd(self._h, in_fd, out_fd, s, report_fd, ctypes.byref(st))
-        else:
-            rc = self._lib.kx_run_records_fd_quoted(self._h, in_fd, out_fd, s, q, report_fd, ctypes.byref(st))
+        with self._batch_actions_for_call(batch_actions):
+            if e is not None:
+                rc = self._lib.kx_run_records_fd_escaped(self._h, in_fd, out_fd, s, -1 if q is None else q, e, report_fd, ctypes.byref(st))
+            elif q is None:
+                rc = self._lib.kx_run_records_fd(self._h, in_fd, out_fd, s, report_fd, ctypes.byref(st))
+            else:
+                rc = self._lib.kx_run_records_fd_quoted(self._h, in_fd, out_fd, s, q, report_fd, ctypes.byref(st))
         self.last_records_stats = st
         if rc not in (0, 1):
             raise EngineError(self._err())
