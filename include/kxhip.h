@@ -281,6 +281,24 @@ int kx_split_records_escaped(const void* d_in, size_t n, uint8_t sep, int quote,
 int kx_run_records_fd_escaped(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, uint8_t escape, int report_fd,
                               kx_records_stats* stats);
 
+/* ---- record mode with a multi-byte separator ----------------------------------------------------------------------------------
+ * The separator rs is 1 to 8 bytes.  Records end after the leftmost, non-overlapping copies of rs, found left to right (the
+ * boundaries of Python's data.split(rs)): in "\n\n\n\n\n" with rs = "\n\n" only every second candidate counts.  The separator
+ * stays in the record, nothing is stripped, a non-empty tail is a last record.  A buffer is split with a context: the last
+ * min(rs_len - 1, length of the unfinished record so far) bytes before it, all of which belong to the unfinished record, so that
+ * a separator may straddle two buffers.  With rs_len = 1 the offsets are kx_split_records's. */
+/* kx_split_records for d_in[0, n) with the separator rs[0, rs_len) and the context ctx_in[0, ctx_in_len) (host pointers).
+   Offsets, capacity and size query as kx_split_records.  On success (return 0) ctx_out[0, *ctx_out_len) (host, room for 7
+   bytes) is the context for the buffer that follows, and *tail_len the bytes of this buffer behind its last selected separator:
+   its last record is complete iff *tail_len == 0.  ctx_out, ctx_out_len and tail_len may be NULL.  rs_len outside 1..8 or
+   ctx_in_len >= rs_len is KX_E_ARG. */
+int kx_split_records_rs(const void* d_in, size_t n, const uint8_t* rs, uint32_t rs_len, const uint8_t* ctx_in, uint32_t ctx_in_len,
+                        uint64_t base, uint64_t* d_off, uint64_t cap, uint64_t* n_records, uint8_t* ctx_out, uint32_t* ctx_out_len,
+                        uint64_t* tail_len, void* stream);
+/* kx_run_records_fd with the multi-byte split; the context carries from window to window (it starts empty). */
+int kx_run_records_fd_rs(kx_program* p, int in_fd, int out_fd, const uint8_t* rs, uint32_t rs_len, int report_fd,
+                         kx_records_stats* stats);
+
 /* ---- sharded execution: one contiguous shard of the input per GPU -------------
  * Per stage and per rank:
  *   kx_shard_begin → kx_shard_forward → [exchange kx_fwd_summary] → kx_shard_fix_head

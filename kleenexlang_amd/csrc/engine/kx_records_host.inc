@@ -7,7 +7,10 @@
 // run as a one-document batch in front of the next window's records.  With a quote byte (kx_run_records_fd_quoted) the split is
 // kx_split_records_quoted, and the quote parity at the end of each window is the parity_in of the next; nothing else differs.
 // With an escape byte (kx_run_records_fd_escaped) the split is kx_split_records_escaped, and the state it ends in (quote parity,
-// escape) is the state_in of the next window's split.
+// escape) is the state_in of the next window's split.  With a multi-byte separator (kx_run_records_fd_rs) the split is
+// kx_split_records_rs, and the context it leaves (the last bytes of the unfinished record, fewer than the separator has) is the
+// context of the next window's split: a separator may straddle windows, and the carried record is then completed by a first
+// record that may be a single byte long.
 
 namespace {
 
@@ -168,6 +171,99 @@ int splitRecordsEscaped(const uint8_t* d_in, size_t n, uint8_t sep, int quote, u
   return 0;
 }
 
+struct RecRsWs {   // grow-only device workspace of a multi-byte split: RecWs plus the per-tile maps / states, counts per state, info
+  RecWs base;
+  BatchWs::Buf tmap, tcnt, info;
+  ~RecRsWs() { for (BatchWs::Buf* b : {&tmap, &tcnt, &info}) if (b->p) (void)hipFree(b->p); }
+};
+
+// no proper prefix of rs is also a suffix: copies of rs cannot overlap
+bool rsBorderFree(const uint8_t* rs, uint32_t m) {
+  for (uint32_t b = 1; b < m; ++b) if (!memcmp(rs, rs + m - b, b)) return false;
+  return true;
+}
+
+// the multi-byte split (1 ≤ m ≤ 8, k < m; rs, ctx, ctx_out host memory); *nsep = selected separators, *nrec = records.  On
+// success *ctx_out_len bytes of ctx_out (7 bytes) = the context for the buffer behind this one and *tail_len = the bytes of this
+// buffer behind its last selected separator (host.split_rs_records_model).
+int splitRecordsRs(const uint8_t* d_in, size_t n, const uint8_t* rs, uint32_t m, const uint8_t* ctx, uint32_t k, uint64_t base,
+                   uint64_t* d_off, uint64_t cap, uint64_t* nrec, uint64_t* nsep, uint8_t* ctx_out, uint32_t* ctx_out_len, uint64_t* tail_len,
+                   RecRsWs& W, hipStream_t sm) {
+  *nrec = 0; *nsep = 0;
+  if (n == 0) {
+    if (cap < 1) return setErr(KX_E_CAPACITY, "kx_split_records_rs: offsets buffer too small");
+    HIPCHECK(hipMemcpyAsync(d_off, &base, 8, hipMemcpyHostToDevice, sm));
+    HIPCHECK(hipStreamSynchronize(sm));
+    memmove(ctx_out, ctx, k);
+    *ctx_out_len = k;
+    *tail_len = 0;
+    return 0;
+  }
+  const uint8_t* a0 = (const uint8_t*)((uintptr_t)d_in & ~(uintptr_t)15);
+  const unsigned long long lo = (unsigned long long)(d_in - a0), hi = lo + n, ng = (hi + 15) / 16;
+  const unsigned long long ntiles = (ng + REC_TILE - 1) / REC_TILE;
+  if (ntiles > 0x7FFFFFFFull) return setErr(KX_E_ARG, "kx_split_records_rs: buffer too large");
+  const bool overlap = !rsBorderFree(rs, m);
+  int rc = BatchWs::ensure(W.base.tcount, ntiles * 8);
+  if (!rc) rc = BatchWs::ensure(W.base.toff, ntiles * 8);
+  if (!rc) rc = BatchWs::ensure(W.base.flags, sizeof(Flags));
+  if (!rc && overlap) rc = BatchWs::ensure(W.tmap, ntiles * 4);
+  if (!rc && overlap) rc = BatchWs::ensure(W.tcnt, ntiles * 32);
+  if (!rc && overlap) rc = BatchWs::ensure(W.info, 4);
+  if (rc) return rc;
+  unsigned long long rs8 = 0, ctx8 = 0;
+  for (uint32_t i = 0; i < m; ++i) rs8 |= (unsigned long long)rs[i] << (8 * i);
+  for (uint32_t i = 0; i < k; ++i) ctx8 |= (unsigned long long)ctx[i] << (8 * i);
+  unsigned long long* tcount = (unsigned long long*)W.base.tcount.p;
+  unsigned long long* toff = (unsigned long long*)W.base.toff.p;
+  if (overlap) {
+    hipLaunchKernelGGL(k_rocount, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, rs8, m, ctx8, k, (uint32_t*)W.tmap.p,
+                       (uint32_t*)W.tcnt.p);
+    hipLaunchKernelGGL(k_rsscan, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, m, (uint32_t*)W.tmap.p, (const uint32_t*)W.tcnt.p, tcount,
+                       (uint32_t*)W.info.p);
+  } else {
+    hipLaunchKernelGGL(k_rbcount, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, rs8, m, ctx8, k, tcount);
+  }
+  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, (const unsigned long long*)tcount, toff, (Flags*)W.base.flags.p);
+  HIPCHECK(hipGetLastError());
+  unsigned long long total = 0;
+  uint32_t info = 0;
+  uint8_t endb[16] = {};   // the context, then the buffer's last nl bytes: every byte that ctx_out or the last candidate can hold
+  const size_t nl = n < 8 ? n : 8;
+  memcpy(endb, ctx, k);
+  HIPCHECK(hipMemcpyAsync(&total, &((Flags*)W.base.flags.p)->total_len, 8, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipMemcpyAsync(endb + k, d_in + n - nl, nl, hipMemcpyDeviceToHost, sm));
+  if (overlap) HIPCHECK(hipMemcpyAsync(&info, W.info.p, 4, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipStreamSynchronize(sm));
+  const uint8_t* end = endb + k + nl;                                   // (behind the buffer's last byte)
+  const size_t known = n < 8 ? k + n : 8;                               // bytes before `end` that belong to the unfinished record or the buffer
+  // border-free: every copy is selected, so the buffer ends in a separator iff its last m bytes (the context's included) are rs
+  const int tail = overlap ? !(info & 1u) : !(known >= m && !memcmp(end - m, rs, m));
+  *nsep = total;
+  *nrec = total + (uint64_t)tail;
+  if (cap < *nrec + 1 || !d_off) return setErr(KX_E_CAPACITY, "kx_split_records_rs: offsets buffer too small");
+  if (overlap)
+    hipLaunchKernelGGL(k_rowrite, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, rs8, m, ctx8, k, (const uint32_t*)W.tmap.p,
+                       (const unsigned long long*)toff, (unsigned long long)base, total, tail, (unsigned long long*)d_off);
+  else
+    hipLaunchKernelGGL(k_rbwrite, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, rs8, m, ctx8, k, (const unsigned long long*)toff,
+                       (unsigned long long)base, total, tail, (unsigned long long*)d_off);
+  HIPCHECK(hipGetLastError());
+  uint64_t e = base;   // the last selected separator's end
+  if (tail && total) HIPCHECK(hipMemcpyAsync(&e, d_off + total, 8, hipMemcpyDeviceToHost, sm));
+  HIPCHECK(hipStreamSynchronize(sm));
+  const uint64_t tl = tail ? n - (e - base) : 0;
+  size_t unfinished = total ? tl : k + n;                               // the unfinished record so far (without a separator: the context's bytes too)
+  if (!tail) unfinished = 0;
+  const size_t co = unfinished < m - 1 ? unfinished : m - 1;            // (≤ 7 ≤ known whenever unfinished ≥ 7)
+  uint8_t tmp[8];
+  memcpy(tmp, end - co, co);
+  memcpy(ctx_out, tmp, co);
+  *ctx_out_len = (uint32_t)co;
+  *tail_len = tl;
+  return 0;
+}
+
 // the compute step of kx_run_records_fd, kx_run_records_fd_quoted and kx_run_records_fd_escaped
 struct RecordsRun {
   kx_program* p = nullptr;
@@ -176,8 +272,11 @@ struct RecordsRun {
   int quote = -1;                                      // the quote byte, -1: none (kx_run_records_fd)
   int escape = -1;                                     // the escape byte, -1: none
   uint32_t state = 0;                                  // at the start of the next window: bit 0 quote parity, bit 1 escaped
+  uint8_t rs[8] = {}, ctx[8] = {};                     // the multi-byte separator (kx_run_records_fd_rs) and the next window's context
+  uint32_t rs_len = 0, ctx_len = 0;                    // rs_len 0: a one-byte mode
   RecQWs qws;
   RecEWs ews;
+  RecRsWs rws;
   int report_fd = -1;
   RecWs ws;
   BatchWs::Buf off, ooff, docs, carry, one, longest;   // offsets; output offsets; doc records; the straddling record; its offsets
@@ -253,7 +352,13 @@ struct RecordsRun {
     if (off.cap < 16) { int rc = BatchWs::ensure(off, (n / 32 + 2) * 8); if (rc) return rc; }
     if (timing) HIPCHECK(hipEventRecord(ev[0], nullptr));
     uint32_t sout = state;
+    uint8_t cout[8] = {};
+    uint32_t cout_len = 0;
+    uint64_t tail_len = 0;
     auto split = [&] {
+      if (rs_len)
+        return splitRecordsRs(in, n, rs, rs_len, ctx, ctx_len, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, cout, &cout_len, &tail_len, rws,
+                              nullptr);
       if (escape >= 0)
         return splitRecordsEscaped(in, n, sep, quote, (uint8_t)escape, state, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, &sout, ews, nullptr);
       return quote < 0 ? splitRecords(in, n, sep, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, ws, nullptr)
@@ -266,6 +371,8 @@ struct RecordsRun {
     }
     if (rc) return rc;
     state = sout;
+    memcpy(ctx, cout, 8);
+    ctx_len = cout_len;
     if (timing) { HIPCHECK(hipEventRecord(ev[1], nullptr)); HIPCHECK(hipEventSynchronize(ev[1])); st.split_ms += evMs(ev[0], ev[1]); }
     const uint64_t complete = last ? nrec : nsep;   // (a tail that is not the stream's end continues in the next window)
     const uint64_t* d_off = (const uint64_t*)off.p;
@@ -391,10 +498,38 @@ extern "C" int kx_split_records_escaped(const void* d_in, size_t n, uint8_t sep,
   return rc;
 }
 
+extern "C" int kx_split_records_rs(const void* d_in, size_t n, const uint8_t* rs, uint32_t rs_len, const uint8_t* ctx_in, uint32_t ctx_in_len,
+                                   uint64_t base, uint64_t* d_off, uint64_t cap, uint64_t* n_records, uint8_t* ctx_out, uint32_t* ctx_out_len,
+                                   uint64_t* tail_len, void* stream) {
+  if (!n_records) return setErr(KX_E_ARG, "null argument");
+  *n_records = 0;
+  if (ctx_out_len) *ctx_out_len = 0;
+  if (tail_len) *tail_len = 0;
+  if (!rs || rs_len < 1 || rs_len > 8) return setErr(KX_E_ARG, "kx_split_records_rs: the separator must be 1 to 8 bytes");
+  if (ctx_in_len >= rs_len || (ctx_in_len && !ctx_in)) return setErr(KX_E_ARG, "kx_split_records_rs: the context must be shorter than the separator");
+  if (n && !d_in) return setErr(KX_E_ARG, "kx_split_records_rs: null input");
+  if (cap && !d_off) return setErr(KX_E_ARG, "kx_split_records_rs: null offsets with a capacity");
+  RecRsWs ws;
+  uint64_t nsep = 0, tl = 0;
+  uint8_t co[8] = {}, ci[8] = {};
+  uint32_t col = 0;
+  if (ctx_in_len) memcpy(ci, ctx_in, ctx_in_len);
+  const int rc = splitRecordsRs((const uint8_t*)d_in, n, rs, rs_len, ci, ctx_in_len, base, d_off, cap, n_records, &nsep, co, &col, &tl, ws,
+                                (hipStream_t)stream);
+  if (rc == 0) {
+    if (ctx_out) memcpy(ctx_out, co, col);
+    if (ctx_out_len) *ctx_out_len = col;
+    if (tail_len) *tail_len = tl;
+  }
+  return rc;
+}
+
 namespace {
 
-// kx_run_records_fd (quote < 0, escape < 0), kx_run_records_fd_quoted (escape < 0) and kx_run_records_fd_escaped
-int runRecordsFd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, int escape, int report_fd, kx_records_stats* stats) {
+// kx_run_records_fd (quote < 0, escape < 0), kx_run_records_fd_quoted (escape < 0), kx_run_records_fd_escaped and, with rs_len > 0,
+// kx_run_records_fd_rs (sep, quote and escape unused)
+int runRecordsFd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, int escape, int report_fd, kx_records_stats* stats,
+                 const uint8_t* rs = nullptr, uint32_t rs_len = 0) {
   if (!p) return setErr(KX_E_ARG, "null argument");
   if (p->cfg.phase) return setErr(KX_E_ARG, "record mode runs every phase: kx_config::phase must be 0");
   const double t_begin = FdStream::nowMs();
@@ -408,6 +543,7 @@ int runRecordsFd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, i
   (void)hipGetDevice(&fsr.dev);
   RecordsRun R;
   R.p = p; R.fs = &fsr; R.sep = sep; R.quote = quote; R.escape = escape; R.report_fd = report_fd;
+  if (rs_len) { memcpy(R.rs, rs, rs_len); R.rs_len = rs_len; }
   R.timing = p->cfg.collect_timing != 0;
   int rc = 0;
   if (R.timing) for (auto& e : R.ev) if (hipEventCreate(&e) != hipSuccess) rc = setErr(KX_E_HIP, "hipEventCreate failed");
@@ -447,4 +583,10 @@ extern "C" int kx_run_records_fd_escaped(kx_program* p, int in_fd, int out_fd, u
   if (escape == sep) return setErr(KX_E_ARG, "kx_run_records_fd_escaped: the escape byte cannot be the separator");
   if (quote == escape) return setErr(KX_E_ARG, "kx_run_records_fd_escaped: the escape byte cannot be the quote byte");
   return runRecordsFd(p, in_fd, out_fd, sep, quote, escape, report_fd, stats);
+}
+
+extern "C" int kx_run_records_fd_rs(kx_program* p, int in_fd, int out_fd, const uint8_t* rs, uint32_t rs_len, int report_fd,
+                                    kx_records_stats* stats) {
+  if (!rs || rs_len < 1 || rs_len > 8) return setErr(KX_E_ARG, "kx_run_records_fd_rs: the separator must be 1 to 8 bytes");
+  return runRecordsFd(p, in_fd, out_fd, 0, -1, -1, report_fd, stats, rs, rs_len);
 }

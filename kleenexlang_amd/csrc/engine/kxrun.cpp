@@ -13,7 +13,8 @@
 // "Match error at input symbol S in record R!" line per rejected record to stderr, and the run goes on to the end.  With
 // `--quote[=Q]` (default a double quote) a separator inside Q-quoted fields ends no record (kx_run_records_fd_quoted).  With
 // `--escape[=E]` (default a backslash) a byte after an unescaped E is only data: never a separator, a quote or an escape
-// (kx_run_records_fd_escaped, with or without --quote).
+// (kx_run_records_fd_escaped, with or without --quote).  With `--rs=STR` the separator is the 1 to 8 bytes STR spells, and records
+// end after its leftmost, non-overlapping copies (kx_run_records_fd_rs).
 //
 // BIN = this executable ++ KXP blob ++ libdir ++ trailer (see kexc main.cpp).
 // The engine is loaded with dlopen so that this file carries no HIP dependency.
@@ -73,6 +74,7 @@ static void usage(const char* name) {
   fprintf(stdout, "- \"%s --records[=SEP]\": runs every line (or SEP-terminated record) as its own input; rejected ones are reported on stderr.\n", name);
   fprintf(stdout, "- \"%s --records[=SEP] --quote[=Q]\": the same, but a SEP inside Q-quoted fields (default Q: \") ends no record.\n", name);
   fprintf(stdout, "- \"%s --records[=SEP] [--quote[=Q]] --escape[=E]\": the same, but a byte after an unescaped E (default E: \\) is only data.\n", name);
+  fprintf(stdout, "- \"%s --records --rs=STR\": records end after the 1 to 8 bytes STR spells (\\r\\n, \\n\\n, \\xHH ...), leftmost and non-overlapping.\n", name);
 }
 
 // --records=SEP, --quote=Q, --escape=E: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
@@ -92,6 +94,32 @@ static bool parseSeparator(const char* a, uint8_t* sep) {
   }
   if (n == 4 && a[0] == '\\' && a[1] == 'x' && hex(a[2]) >= 0 && hex(a[3]) >= 0) { *sep = (uint8_t)(hex(a[2]) * 16 + hex(a[3])); return true; }
   return false;
+}
+
+// --rs=STR: 1 to 8 byte spellings, each a literal byte or \n \t \r \0 \\ \xHH; a backslash always starts an escape.  false if
+// STR is not that; else *len bytes in rs.
+static bool parseSeparatorString(const char* a, uint8_t* rs, uint32_t* len) {
+  auto hex = [](char c) { return c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1; };
+  uint32_t n = 0;
+  for (const char* p = a; *p;) {
+    if (n == 8) return false;
+    if (*p != '\\') { rs[n++] = (uint8_t)*p++; continue; }
+    switch (p[1]) {
+      case 'n': rs[n++] = '\n'; p += 2; break;
+      case 't': rs[n++] = '\t'; p += 2; break;
+      case 'r': rs[n++] = '\r'; p += 2; break;
+      case '0': rs[n++] = 0; p += 2; break;
+      case '\\': rs[n++] = '\\'; p += 2; break;
+      case 'x':
+        if (hex(p[2]) < 0 || hex(p[3]) < 0) return false;   // (a NUL ends the test early: hex('\0') < 0)
+        rs[n++] = (uint8_t)(hex(p[2]) * 16 + hex(p[3]));
+        p += 4;
+        break;
+      default: return false;
+    }
+  }
+  *len = n;
+  return n >= 1;
 }
 
 int main(int argc, char** argv) {
@@ -116,9 +144,10 @@ int main(int argc, char** argv) {
 
   static struct option long_options[] = {{"phase", required_argument, 0, 'p'}, {"gpus", required_argument, 0, 'g'},
                                          {"records", optional_argument, 0, 'r'}, {"quote", optional_argument, 0, 'q'},
-                                         {"escape", optional_argument, 0, 'e'}, {0, 0, 0, 0}};
-  bool timing = false, records = false, quoted = false, escaped = false;
-  uint8_t sep = '\n', quote = '"', escape = '\\';
+                                         {"escape", optional_argument, 0, 'e'}, {"rs", required_argument, 0, 's'}, {0, 0, 0, 0}};
+  bool timing = false, records = false, quoted = false, escaped = false, sep_given = false, multi = false;
+  uint8_t sep = '\n', quote = '"', escape = '\\', rs[8] = {};
+  uint32_t rs_len = 0;
   long phase = 0, gpus = 0;
   int c;
   while ((c = getopt_long(argc, argv, "ihtp:", long_options, nullptr)) != -1) {
@@ -136,6 +165,7 @@ int main(int argc, char** argv) {
       case 'p': phase = atol(optarg); if (phase < 1) { fprintf(stderr, "Invalid phase: %ld given\n", phase); return 1; } break;
       case 'r':
         records = true;
+        if (optarg) sep_given = true;
         if (optarg && !parseSeparator(optarg, &sep)) { fprintf(stderr, "Invalid record separator: %s\n", optarg); return 1; }
         break;
       case 'q':
@@ -145,6 +175,10 @@ int main(int argc, char** argv) {
       case 'e':
         escaped = true;
         if (optarg && !parseSeparator(optarg, &escape)) { fprintf(stderr, "Invalid escape character: %s\n", optarg); return 1; }
+        break;
+      case 's':
+        multi = true;
+        if (!parseSeparatorString(optarg, rs, &rs_len)) { fprintf(stderr, "Invalid record separator: %s\n", optarg); return 1; }
         break;
       case 'h':
       default: usage(argv[0]); return 1;
@@ -158,6 +192,9 @@ int main(int argc, char** argv) {
   if (escaped && !records) { fprintf(stderr, "%s: --escape needs --records\n", argv[0]); return 1; }
   if (escaped && escape == sep) { fprintf(stderr, "%s: the escape character cannot be the record separator\n", argv[0]); return 1; }
   if (escaped && quoted && escape == quote) { fprintf(stderr, "%s: the escape character cannot be the quote character\n", argv[0]); return 1; }
+  if (multi && !records) { fprintf(stderr, "%s: --rs needs --records\n", argv[0]); return 1; }
+  if (multi && sep_given) { fprintf(stderr, "%s: --rs cannot be combined with --records=SEP\n", argv[0]); return 1; }
+  if (multi && (quoted || escaped)) { fprintf(stderr, "%s: --rs cannot be combined with --quote or --escape\n", argv[0]); return 1; }
   struct timeval t0, t1;
   if (timing) gettimeofday(&t0, nullptr);
 
@@ -179,14 +216,20 @@ int main(int argc, char** argv) {
     if (quoted && !runq) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_quoted (--quote needs a newer engine library)\n", argv[0]); return 1; }
     auto rune = (int (*)(kx_program*, int, int, uint8_t, int, uint8_t, int, kx_records_stats*))dlsym(h, "kx_run_records_fd_escaped");
     if (escaped && !rune) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_escaped (--escape needs a newer engine library)\n", argv[0]); return 1; }
+    int (*runm)(kx_program*, int, int, const uint8_t*, uint32_t, int, kx_records_stats*) = nullptr;
+    if (multi) {
+      runm = (decltype(runm))dlsym(h, "kx_run_records_fd_rs");
+      if (!runm) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_rs (--rs needs a newer engine library)\n", argv[0]); return 1; }
+    }
     // record mode is where the single-document route is unusable (a third of a millisecond per record): stages with register
     // actions are replayed by the batch kernels unless KX_BATCH_ACTIONS=0 asks for the route
     if (!cfg.batch_actions) cfg.batch_actions = 2;
     kx_program* prog = nullptr;
     if (load(blob.data(), blob.size(), &cfg, &prog)) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 1; }
-    kx_records_stats rs;
-    if (escaped) rc = rune(prog, STDIN_FILENO, STDOUT_FILENO, sep, quoted ? (int)quote : -1, escape, STDERR_FILENO, &rs);
-    else rc = quoted ? runq(prog, STDIN_FILENO, STDOUT_FILENO, sep, quote, STDERR_FILENO, &rs) : runr(prog, STDIN_FILENO, STDOUT_FILENO, sep, STDERR_FILENO, &rs);
+    kx_records_stats rs_stats;
+    if (multi) rc = runm(prog, STDIN_FILENO, STDOUT_FILENO, rs, rs_len, STDERR_FILENO, &rs_stats);
+    else if (escaped) rc = rune(prog, STDIN_FILENO, STDOUT_FILENO, sep, quoted ? (int)quote : -1, escape, STDERR_FILENO, &rs_stats);
+    else rc = quoted ? runq(prog, STDIN_FILENO, STDOUT_FILENO, sep, quote, STDERR_FILENO, &rs_stats) : runr(prog, STDIN_FILENO, STDOUT_FILENO, sep, STDERR_FILENO, &rs_stats);
     if (rc != 0 && rc != KX_MATCH_ERROR) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 1; }
     if (timing) {   // (a rejected record does not end the run: the time is printed either way)
       gettimeofday(&t1, nullptr);

@@ -312,6 +312,49 @@ def split_escaped_records_model(data, sep=b"\n", quote=None, escape=b"\\", state
     return offs, p | x << 1
 
 
+def _check_rs(rs):
+    """A multi-byte record separator: bytes of length 1 to 8 → bytes.  Raises TypeError / ValueError."""
+    if not isinstance(rs, (bytes, bytearray)):
+        raise TypeError("record separator string: bytes of length 1 to 8, not %s" % type(rs).__name__)
+    if not 1 <= len(rs) <= 8:
+        raise ValueError("record separator string: 1 to 8 bytes, not %d" % len(rs))
+    return bytes(rs)
+
+
+def _check_ctx(ctx, rs):
+    if not isinstance(ctx, (bytes, bytearray)):
+        raise TypeError("context: bytes shorter than the separator, not %s" % type(ctx).__name__)
+    if len(ctx) >= len(rs):
+        raise ValueError("context: %d bytes, not shorter than the separator (%d)" % (len(ctx), len(rs)))
+    return bytes(ctx)
+
+
+def split_rs_records_model(data, rs, ctx=b""):
+    """kx_split_records_rs in pure Python: (offsets, ctx_out, tail_len).  Records end after the leftmost, non-overlapping copies
+    of `rs` (1 to 8 bytes), found left to right as bytes.find finds them: the boundaries of data.split(rs).  `ctx` is the last
+    min(len(rs) - 1, length of the unfinished record so far) bytes before data, all of the unfinished record, so that a separator
+    may straddle two buffers; ctx_out is the context for the buffer that follows, tail_len the bytes of data behind its last
+    selected separator (the last record is complete iff it is 0).  A non-empty tail is a last record, as in split_records_model."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError("split_rs_records_model: data must be bytes, not %s" % type(data).__name__)
+    rs = _check_rs(rs)
+    ctx = _check_ctx(ctx, rs)
+    data = bytes(data)
+    m, k, buf = len(rs), len(ctx), ctx + data
+    offs, pos = [0], 0
+    while True:
+        j = buf.find(rs, pos)
+        if j < 0:
+            break
+        pos = j + m                                  # always > k: ctx is shorter than rs
+        offs.append(pos - k)
+    tail_len = len(data) - max(pos - k, 0)           # bytes of this buffer behind its last selected separator
+    if offs[-1] != len(data):
+        offs.append(len(data))
+    t = buf[pos:]
+    return offs, t[len(t) - min(m - 1, len(t)):], tail_len
+
+
 def _check_values(values, what):
     import torch
     if not isinstance(values, torch.Tensor):
@@ -392,6 +435,31 @@ def split_escaped_records_tensor(values, sep=b"\n", quote=None, escape=b"\\", st
     if rc:
         raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
     return off, sout.value
+
+
+def split_rs_records_tensor(values, rs, ctx=b""):
+    """kx_split_records_rs: split_records_tensor for a separator `rs` of 1 to 8 bytes (split_rs_records_model); `ctx` is the
+    context before values[0].  Returns (offsets, (ctx_out, tail_len))."""
+    _check_values(values, "split_rs_records_tensor")
+    rs = _check_rs(rs)
+    ctx = _check_ctx(ctx, rs)
+    import torch
+    if not values.is_cuda:
+        raise EngineError("split_rs_records_tensor: values must be on a HIP device (there is no CPU fallback)")
+    lib = load_engine()
+    stream = ctypes.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)
+    vptr = ctypes.c_void_p(values.data_ptr() if values.numel() else None)
+    n, col, tl = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint64()
+    cout = (ctypes.c_uint8 * 8)()
+    rc = lib.kx_split_records_rs(vptr, values.numel(), rs, len(rs), ctx, len(ctx), 0, None, 0, ctypes.byref(n), None, None, None, stream)
+    if rc not in (0, -3):
+        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
+    off = torch.empty(n.value + 1, dtype=torch.int64, device=values.device)
+    rc = lib.kx_split_records_rs(vptr, values.numel(), rs, len(rs), ctx, len(ctx), 0, ctypes.c_void_p(off.data_ptr()), off.numel(),
+                                 ctypes.byref(n), cout, ctypes.byref(col), ctypes.byref(tl), stream)
+    if rc:
+        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
+    return off, (bytes(cout[:col.value]), tl.value)
 
 
 class KxDfInfo(ctypes.Structure):
@@ -489,6 +557,10 @@ def load_engine():
                                                  ctypes.POINTER(u64), ctypes.POINTER(u32), vp]
         lib.kx_run_records_fd_escaped.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint8, ctypes.c_int, ctypes.c_uint8,
                                                   ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
+        lib.kx_split_records_rs.argtypes = [vp, sz, ctypes.c_char_p, u32, ctypes.c_char_p, u32, u64, vp, u64, ctypes.POINTER(u64),
+                                            ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(u32), ctypes.POINTER(u64), vp]
+        lib.kx_run_records_fd_rs.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, u32, ctypes.c_int,
+                                             ctypes.POINTER(KxRecordsStats)]
         lib.kx_shard_begin.argtypes = [vp, u32, vp, sz, ctypes.c_int, ctypes.c_int, vp, ctypes.POINTER(vp)]
         lib.kx_shard_forward.argtypes = [vp, ctypes.POINTER(KxFwdSummary)]
         lib.kx_shard_fix_head.argtypes = [vp, u32, ctypes.POINTER(KxFwdSummary)]
@@ -988,14 +1060,28 @@ class Program:
                 self._cfg.batch_actions = old
                 self._lib.kx_set_config(self._h, ctypes.byref(self._cfg))
 
-    def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None, batch_actions=True):
+    @staticmethod
+    def _check_rs_alone(rs, sep, quote, escape, what):
+        """The `rs=` keyword of record mode: 1 to 8 bytes, with the default `sep` and neither `quote` nor `escape`."""
+        rs = _check_rs(rs)
+        if _check_sep(sep) != 0x0A:
+            raise ValueError("%s: rs= cannot be combined with sep=" % what)
+        if quote is not None or escape is not None:
+            raise ValueError("%s: rs= cannot be combined with quote= or escape=" % what)
+        return rs
+
+    def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None, batch_actions=True, rs=None):
         """Record mode on bytes: every record of `data` (split after each `sep` byte, kx_split_records on the device) is a
         whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage).  With a `quote` byte
         a separator inside quotes ends no record (kx_split_records_quoted from parity 0).  With an `escape` byte an escaped
         byte is only data (kx_split_records_escaped from state 0).  `batch_actions`: stages with register actions are replayed
-        by the batch kernels (kx_config::batch_actions = 2 for this call) instead of routing every record."""
+        by the batch kernels (kx_config::batch_actions = 2 for this call) instead of routing every record.  With `rs` (1 to 8
+        bytes; not with a `sep`, `quote` or `escape`) records end after the leftmost, non-overlapping copies of rs
+        (kx_split_records_rs from an empty context)."""
         if not isinstance(data, (bytes, bytearray, memoryview)):
             raise TypeError("run_records: data must be bytes, not %s" % type(data).__name__)
+        if rs is not None:
+            rs = self._check_rs_alone(rs, sep, quote, escape, "run_records")
         _check_sep(sep)
         if quote is not None:
             _check_quote(quote, sep)
@@ -1005,7 +1091,9 @@ class Program:
         data = bytes(data)
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         v = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else torch.empty(0, dtype=torch.uint8, device=dev)
-        if escape is not None:
+        if rs is not None:
+            offs = split_rs_records_tensor(v, rs)[0]
+        elif escape is not None:
             offs = split_escaped_records_tensor(v, sep, quote, escape)[0]
         else:
             offs = split_records_tensor(v, sep) if quote is None else split_quoted_records_tensor(v, sep, quote)[0]
@@ -1016,20 +1104,25 @@ class Program:
         ooff, status, fpos, fstage = ooff.tolist(), status.tolist(), fpos.tolist(), fstage.tolist()
         return [MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]] for i in range(len(status))]
 
-    def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None, batch_actions=True):
+    def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None, batch_actions=True, rs=None):
         """kx_run_records_fd: the stream on in_fd in record mode, outputs to out_fd, one line per rejected record to report_fd
         (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected.  With a `quote`
         byte, kx_run_records_fd_quoted: a separator inside quotes ends no record.  With an `escape` byte,
-        kx_run_records_fd_escaped: an escaped byte is only data (with or without a quote).  `batch_actions` as in run_records."""
+        kx_run_records_fd_escaped: an escaped byte is only data (with or without a quote).  With `rs` (1 to 8 bytes),
+        kx_run_records_fd_rs: records end after the leftmost, non-overlapping copies of rs.  `batch_actions` as in run_records."""
         for name, fd in (("in_fd", in_fd), ("out_fd", out_fd), ("report_fd", report_fd)):
             if isinstance(fd, bool) or not isinstance(fd, int):
                 raise TypeError("run_records_fd: %s must be an int file descriptor, not %s" % (name, type(fd).__name__))
+        if rs is not None:
+            rs = self._check_rs_alone(rs, sep, quote, escape, "run_records_fd")
         s = _check_sep(sep)
         q = None if quote is None else _check_quote(quote, sep)
         e = None if escape is None else _check_escape(escape, sep, quote)
         st = KxRecordsStats()
         with self._batch_actions_for_call(batch_actions):
-            if e is not None:
+            if rs is not None:
+                rc = self._lib.kx_run_records_fd_rs(self._h, in_fd, out_fd, rs, len(rs), report_fd, ctypes.byref(st))
+            elif e is not None:
                 rc = self._lib.kx_run_records_fd_escaped(self._h, in_fd, out_fd, s, -1 if q is None else q, e, report_fd, ctypes.byref(st))
             elif q is None:
                 rc = self._lib.kx_run_records_fd(self._h, in_fd, out_fd, s, report_fd, ctypes.byref(st))
