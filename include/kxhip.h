@@ -230,6 +230,27 @@ typedef struct kx_batch_stats {
 int kx_run_batch(kx_program* prog, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, void* d_out, size_t cap,
                  uint64_t* d_out_off, kx_batch_doc* d_docs, size_t* out_len, kx_batch_stats* stats, void* stream);
 
+/* ---- framed batches: documents that end before the next one starts, outputs that end in a terminator ---------------------------
+ * kx_run_batch with a frame.  Document i is d_in[d_in_off[i], d_in_off[i+1] - trim): the last `trim` bytes of every range (a
+ * record separator, say) belong to no document; with last_whole != 0 document n_docs - 1 is not trimmed (a last record without a
+ * separator).  The trim applies to the input of stage 0 only.  The suffix[0, suffix_len) bytes follow the output of every ACCEPTED
+ * document — one whose output is empty included — inside its range of d_out_off; a rejected document's range stays empty.  The
+ * suffix is added behind the last stage only.  Everything else is kx_run_batch: a document's result (output, fail_pos) is what
+ * kx_run_device gives for the trimmed document alone; *out_len, KX_E_CAPACITY, the size query and stats->out_bytes count the
+ * suffixes.  frame == NULL or an all-zero frame IS kx_run_batch, bit for bit.
+ * KX_E_ARG besides kx_run_batch's: a trimmed range shorter than `trim` (found on the device, with the decreasing offsets, before
+ * any kernel reads a document), suffix_len > 8, a non-zero reserved word. */
+typedef struct kx_batch_frame {
+  uint32_t trim;         /* bytes cut from the end of every document's range                       */
+  uint32_t last_whole;   /* != 0: the last document keeps its whole range                          */
+  uint32_t suffix_len;   /* 0 to 8                                                                 */
+  uint8_t suffix[8];
+  uint32_t reserved[3];  /* must be 0 */
+} kx_batch_frame;
+int kx_run_batch_framed(kx_program* prog, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_frame* frame,
+                        void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs, size_t* out_len, kx_batch_stats* stats,
+                        void* stream);
+
 /* ---- record mode: every separator-terminated record of a stream as its own input ----------------------------------------
  * A record is the bytes up to and including a separator byte; a non-empty tail after the last separator is a last record;
  * empty input has no records.  Each record's result is what kx_run_device gives for it alone (every stage runs). */
@@ -298,6 +319,35 @@ int kx_split_records_rs(const void* d_in, size_t n, const uint8_t* rs, uint32_t 
 /* kx_run_records_fd with the multi-byte split; the context carries from window to window (it starts empty). */
 int kx_run_records_fd_rs(kx_program* p, int in_fd, int out_fd, const uint8_t* rs, uint32_t rs_len, int report_fd,
                          kx_records_stats* stats);
+
+/* ---- record mode, framing apart from the program: strip the separator, append an output separator ---------------------------
+ * kx_run_records_fd_opts is the four entry points above in one, plus:
+ *   chomp    every record is run WITHOUT its separator (1 byte, or rs_len bytes in KX_RECORDS_RS mode).  A last record that is a
+ *            tail has no valid separator and is run whole — under a quote or an escape byte it may end in a separator byte that
+ *            is quoted or escaped: that byte is data and stays.  A record that is only its separator is the empty document: run,
+ *            not skipped.  S of the report line counts inside the chomped record.
+ *   ors      ors_len (0 to 8) bytes that follow the output of every accepted record (a tail and an empty output included); a
+ *            rejected record writes nothing.  kx_records_stats::out_bytes counts them.
+ * With a pipeline the separator is cut in front of stage 0 and ors added behind the last stage (kx_run_batch_framed).  With
+ * chomp = 0 and ors_len = 0 the call is the entry point of its mode above.  `size` must be sizeof(kx_records_opts); the fields a
+ * mode does not use are ignored, except that quote / escape are "-1: none" in KX_RECORDS_ESCAPED.  KX_E_ARG: a wrong size or mode,
+ * what the mode's own entry point refuses, ors_len > 8, a non-zero reserved word. */
+enum { KX_RECORDS_BYTE = 0, KX_RECORDS_QUOTED = 1, KX_RECORDS_ESCAPED = 2, KX_RECORDS_RS = 3 };
+typedef struct kx_records_opts {
+  uint32_t size;       /* sizeof(kx_records_opts) */
+  uint32_t mode;       /* KX_RECORDS_* */
+  uint8_t sep;         /* BYTE, QUOTED, ESCAPED */
+  uint8_t pad[3];      /* must be 0 */
+  int32_t quote;       /* QUOTED: a byte value; ESCAPED: a byte value or -1 */
+  int32_t escape;      /* ESCAPED: a byte value */
+  uint8_t rs[8];       /* RS */
+  uint32_t rs_len;     /* RS: 1 to 8 */
+  uint32_t chomp;      /* 0 / 1 */
+  uint8_t ors[8];
+  uint32_t ors_len;    /* 0 to 8 */
+  uint32_t reserved[4];   /* must be 0 */
+} kx_records_opts;
+int kx_run_records_fd_opts(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, int report_fd, kx_records_stats* stats);
 
 /* ---- sharded execution: one contiguous shard of the input per GPU -------------
  * Per stage and per rank:

@@ -24,15 +24,37 @@
 // [r/32 + i, r/32 + i + n_i/32] and piece slots [r/64 + i, (r + n_i)/64 + i + 1) — floor(a) + floor(b) <= floor(a + b) keeps the
 // ranges of consecutive documents apart.  Every slot of a document's piece range is written by k_bback (unused ones marked), so
 // k_bemit can take the slots as its lanes without a memset.
+//
+// Framed batches (kx_run_batch_framed): k_bcheck / k_bforward / k_bback end in a parameter pack FR that is empty or one BFrame,
+// and k_bemit has a twin, k_bemit_fr, that takes one.  The framed instances take document i of stage 0 as
+// in[off[i], off[i+1] - trim) (one document may be left whole); the instances without a frame are the kernels of kx_run_batch.
+// The slot bases above still come from the UNTRIMMED starts, so the ranges stay apart; a trimmed document may need one slot fewer
+// than its range holds, which k_bback marks unused like any other.  bload_piece gets the trimmed end, so a lane still loads only
+// the granules of its own (trimmed) document.  A suffix is no business of these kernels: BDoc::len stays the document's own
+// output length, the scan adds the suffix to the length of every accepted document (k_bscan_*'s sfx), and k_bsuffix writes its
+// bytes at the end of the document's output range.
 
 constexpr uint32_t BATCH_BT = 512;     // threads per workgroup of the per-document kernels
 constexpr uint32_t BATCH_NO_DOC = 0xFFFFFFFFu;
-enum { BC_ROUTED = 0, BC_REJECTED = 1, BC_BADOFF = 2, BC_N = 4 };
+enum { BC_ROUTED = 0, BC_REJECTED = 1, BC_BADOFF = 2, BC_SHORT = 3, BC_N = 4 };
 
 struct __attribute__((aligned(16))) BDoc { unsigned long long len; uint32_t endh; uint16_t mode; uint16_t l0; };   // mode: BM_*
 enum { BM_RUN = 0, BM_SKIP = 1, BM_ROUTED = 2 };
 struct __attribute__((aligned(8))) BRoute { unsigned long long start, len; uint32_t doc, rejected; unsigned long long fail; };
 struct __attribute__((aligned(16))) BRec { uint32_t doc, leaf4; unsigned long long cum; };   // cum: output bytes of the steps behind the piece
+
+// the frame of a stage's input: the last `trim` bytes of every document's range are not the document's, except for document `whole`
+struct BFrame { unsigned long long trim, whole; };
+constexpr unsigned long long BATCH_NO_WHOLE = ~0ull;
+// the length of document i, whose range holds n bytes; fr: nothing, or the stage's BFrame
+template <typename... FR>
+__device__ __forceinline__ unsigned long long bdoc_len(unsigned long long n, unsigned long long i, const FR&... fr) {
+  static_assert(sizeof...(FR) <= 1, "at most one frame");
+  if constexpr (sizeof...(FR) != 0) {
+    const BFrame& f = (fr, ...);
+    return n - (i == f.whole ? 0ull : f.trim);
+  } else return n;
+}
 
 __device__ __forceinline__ unsigned long long bchk_base(unsigned long long rel, unsigned long long i) { return (rel >> 5) + i; }
 __device__ __forceinline__ unsigned long long bpiece_base(unsigned long long rel, unsigned long long i) { return (rel >> 6) + i; }
@@ -58,25 +80,30 @@ __device__ __forceinline__ void bload_piece(const uint8_t* p, const uint8_t* end
   for (int i = 0; i < 16; ++i) w[i] = __builtin_amdgcn_alignbyte(x[i + 1], x[i], r);
 }
 
+template <typename... FR>
 __global__ void k_bcheck(const unsigned long long* __restrict__ off, unsigned long long ndocs, kx_batch_doc* __restrict__ rec,
-                         unsigned long long* __restrict__ ctr) {
+                         unsigned long long* __restrict__ ctr, FR... fr) {
   const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= ndocs) return;
   if (off[i + 1] < off[i]) atomicOr(&ctr[BC_BADOFF], 1ull);
+  else if constexpr (sizeof...(FR) != 0) {   // a range shorter than what is cut from it
+    const BFrame& f = (fr, ...);
+    if (i != f.whole && off[i + 1] - off[i] < f.trim) atomicOr(&ctr[BC_SHORT], 1ull);
+  }
   rec[i] = kx_batch_doc{0, 0, 0};
 }
 
-template <bool WIDE>
+template <bool WIDE, typename... FR>
 __global__ __launch_bounds__(BATCH_BT) void k_bforward(const uint8_t* __restrict__ in, const unsigned long long* __restrict__ off,
                                                        unsigned long long ndocs, unsigned long long doc_max, int route_all, uint32_t stage,
                                                        BDoc* __restrict__ docs, kx_batch_doc* __restrict__ rec, uint16_t* __restrict__ chk,
-                                                       BRoute* __restrict__ routes, unsigned long long* __restrict__ ctr, DevTables T) {
+                                                       BRoute* __restrict__ routes, unsigned long long* __restrict__ ctr, DevTables T, FR... fr) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   Lds L = stage_tables<WIDE>(T, smem);
   const unsigned long long o0 = off[0];
   const uint32_t dead = T.deadh;
   for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < ndocs; i += (unsigned long long)gridDim.x * blockDim.x) {
-    const unsigned long long s = off[i], n = off[i + 1] - s;
+    const unsigned long long s = off[i], n = bdoc_len(off[i + 1] - s, i, fr...);
     BDoc d{0, 0, BM_RUN, 0};
     if (rec[i].status) { d.mode = BM_SKIP; docs[i] = d; continue; }   // rejected by an earlier stage: not run (not even as an empty document)
     if (route_all || n > doc_max) {
@@ -127,15 +154,15 @@ __global__ __launch_bounds__(BATCH_BT) void k_bforward(const uint8_t* __restrict
   }
 }
 
-template <bool WIDE>
+template <bool WIDE, typename... FR>
 __global__ __launch_bounds__(BATCH_BT) void k_bback(const uint8_t* __restrict__ in, const unsigned long long* __restrict__ off,
                                                     unsigned long long ndocs, BDoc* __restrict__ docs, const uint16_t* __restrict__ chk,
-                                                    BRec* __restrict__ brec, DevTables T) {
+                                                    BRec* __restrict__ brec, DevTables T, FR... fr) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   Lds L = stage_tables<WIDE>(T, smem);
   const unsigned long long o0 = off[0];
   for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < ndocs; i += (unsigned long long)gridDim.x * blockDim.x) {
-    const unsigned long long s = off[i], n = off[i + 1] - s, rel = s - o0;
+    const unsigned long long s = off[i], n = bdoc_len(off[i + 1] - s, i, fr...), rel = s - o0;
     const unsigned long long pb = bpiece_base(rel, i), pe = bpiece_base(off[i + 1] - o0, i + 1);
     BDoc d = docs[i];
     unsigned long long np = 0;
@@ -159,7 +186,7 @@ __global__ __launch_bounds__(BATCH_BT) void k_bback(const uint8_t* __restrict__ 
       d.len = cum + T.init_len[leaf >> 2];
       docs[i] = d;
     }
-    for (unsigned long long k = pb + np; k < pe; ++k) brec[k].doc = BATCH_NO_DOC;
+    for (unsigned long long k = pb + np; k < pe; ++k) brec[k].doc = BATCH_NO_DOC;   // (pe from the untrimmed end: a trimmed document's spare slot too)
   }
 }
 
@@ -177,10 +204,20 @@ __global__ void k_broute_set(uint32_t nr, const BRoute* __restrict__ res, uint32
 }
 
 // exclusive scan of the document lengths: per-workgroup sums, k_scan_groups, then inside each workgroup.  ooff[ndocs] = total.
-__global__ __launch_bounds__(1024) void k_bscan_reduce(unsigned long long ndocs, const BDoc* __restrict__ docs, unsigned long long* __restrict__ wsum) {
+// sfx != 0 (the last stage of a framed batch): every accepted document's length counts sfx more bytes, its suffix (BDoc::len itself stays)
+__device__ __forceinline__ unsigned long long bscan_len(unsigned long long i, unsigned long long ndocs, const BDoc* __restrict__ docs,
+                                                        const kx_batch_doc* __restrict__ rec, unsigned long long sfx) {
+  if (i >= ndocs) return 0;
+  unsigned long long v = docs[i].len;
+  if (sfx && rec[i].status == 0) v += sfx;
+  return v;
+}
+
+__global__ __launch_bounds__(1024) void k_bscan_reduce(unsigned long long ndocs, const BDoc* __restrict__ docs, unsigned long long* __restrict__ wsum,
+                                                       const kx_batch_doc* __restrict__ rec, unsigned long long sfx) {
   __shared__ unsigned long long red[1024];
   const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  red[threadIdx.x] = i < ndocs ? docs[i].len : 0;
+  red[threadIdx.x] = bscan_len(i, ndocs, docs, rec, sfx);
   __syncthreads();
   for (uint32_t s = blockDim.x >> 1; s > 0; s >>= 1) {
     if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
@@ -190,10 +227,11 @@ __global__ __launch_bounds__(1024) void k_bscan_reduce(unsigned long long ndocs,
 }
 
 __global__ __launch_bounds__(1024) void k_bscan_down(unsigned long long ndocs, const BDoc* __restrict__ docs, const unsigned long long* __restrict__ woff,
-                                                     const Flags* __restrict__ flags, unsigned long long* __restrict__ ooff) {
+                                                     const Flags* __restrict__ flags, unsigned long long* __restrict__ ooff,
+                                                     const kx_batch_doc* __restrict__ rec, unsigned long long sfx) {
   __shared__ unsigned long long buf[1024];
   const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  const unsigned long long v = i < ndocs ? docs[i].len : 0;
+  const unsigned long long v = bscan_len(i, ndocs, docs, rec, sfx);
   buf[threadIdx.x] = v;
   __syncthreads();
   for (uint32_t d = 1; d < blockDim.x; d <<= 1) {
@@ -265,6 +303,34 @@ __global__ __launch_bounds__(BATCH_BT) void k_bemit(const uint8_t* __restrict__ 
   }
 }
 
+// k_bemit for stage 0 of a framed batch: k_bemit's body with the trimmed length — KEEP THE TWO IN STEP, a change to one is a
+// change to both.  Two kernels and not one shared inline body: with a shared body the register allocation of k_bemit<true>
+// differs from the one DESIGN.md §2h records (123 VGPRs / 63 SGPRs, not 121 / 65).
+template <bool WIDE, typename... FR>
+__global__ __launch_bounds__(BATCH_BT) void k_bemit_fr(const uint8_t* __restrict__ in, const unsigned long long* __restrict__ off,
+                                                    unsigned long long nslots, const BDoc* __restrict__ docs, const uint16_t* __restrict__ chk,
+                                                    const BRec* __restrict__ brec, const unsigned long long* __restrict__ ooff,
+                                                    uint8_t* __restrict__ out, DevTables T, FR... fr) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+  Lds L = stage_tables<WIDE>(T, smem);
+  const unsigned long long o0 = off[0];
+  for (unsigned long long j = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; j < nslots; j += (unsigned long long)gridDim.x * blockDim.x) {
+    const BRec r = brec[j];
+    if (r.doc == BATCH_NO_DOC) continue;
+    const unsigned long long i = r.doc, s = off[i], n = bdoc_len(off[i + 1] - s, i, fr...), rel = s - o0;
+    const unsigned long long k = j - bpiece_base(rel, i), ps = k * PIECE;
+    const int plen = n - ps < PIECE ? (int)(n - ps) : PIECE;
+    uint32_t w[16], bo[BOW];
+    bload_piece(in + s + ps, in + s + n, w);
+    piece_forward(w, chk[bchk_base(rel, i) + 2 * k], L, bo);
+    mask_tail(bo, plen, T.nullrow);
+    if (T.xlat) xlat_piece(w, L.base + T.xlat);   // one symbol table on every copying entry: translate the piece once
+    uint8_t* o = out + ooff[i] + docs[i].len - r.cum;
+    uint32_t leaf = r.leaf4;
+    static_for<0, PIECE>([&](auto tc) { bemit_step<PIECE - 1 - decltype(tc)::value, WIDE>(bo, w, leaf, o, L, T); });
+  }
+}
+
 // workgroup = routed document: its output (at src in the route's scratch) to its place
 __global__ void k_bplace(const BRoute* __restrict__ res, const uint8_t* __restrict__ scratch, const unsigned long long* __restrict__ ooff,
                          uint8_t* __restrict__ out) {
@@ -273,6 +339,19 @@ __global__ void k_bplace(const BRoute* __restrict__ res, const uint8_t* __restri
   uint8_t* d = out + ooff[r.doc];
   const uint8_t* sp = scratch + r.start;
   for (unsigned long long k = threadIdx.x; k < r.len; k += blockDim.x) d[k] = sp[k];
+}
+
+// lane = document: the suffix of an accepted document, the last `len` (1 to 8) bytes of its output range (any alignment).  The scan
+// gave every accepted document those bytes, so the stores stay inside the document's own range.  Every kernel that places
+// output (k_bemit, k_bplace, the batch replay) stops where the document's own bytes end, so its order against them is free.
+__global__ void k_bsuffix(unsigned long long ndocs, const kx_batch_doc* __restrict__ rec, const unsigned long long* __restrict__ ooff,
+                          uint8_t* __restrict__ out, unsigned long long sfx8, uint32_t len) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ndocs || rec[i].status) return;
+  const unsigned long long b = ooff[i], e = ooff[i + 1];
+  if (e - b < len) return;   // (never: the scan counted the suffix)
+  uint8_t* o = out + e - len;
+  for (uint32_t j = 0; j < len; ++j) o[j] = (uint8_t)(sfx8 >> (8 * j));
 }
 
 // ---------------------------------------------------------------------------- host-side workspace of kx_run_batch

@@ -10,6 +10,12 @@
 // STREAMS in a workspace batch; k_bact_measure → the scan again, now over the replayed lengths → k_bact_lanes + k_bact_waves
 // write every document's replayed bytes to their final place.  One more round trip (the replayed total and the class counts).
 // With batch_actions = 0 / 1 every document of such a stage goes through batchRouteOne.
+//
+// A framed batch (kx_run_batch_framed): stage 0 runs the <…, BFrame> instances of the kernels with the frame's trim (every later
+// stage and every unframed call the instances without a frame, which are the kernels of before), and the route gets the trimmed lengths.  In the last stage the scan of the output
+// lengths counts the suffix for every accepted document and k_bsuffix writes it next to the kernels that place output (inside
+// emit_ms, or actions_ms for a replayed stage); the documents' own lengths (BDoc::len, BRoute::len) never include it.
+// kx_batch_stats::in_bytes is the bytes of the ranges, the trimmed ones included.
 
 namespace {
 
@@ -72,7 +78,8 @@ int batchRouteOne(kx_program* p, uint32_t st, const uint8_t* d_doc, uint64_t n, 
 // the caller's d_out for the last stage, else the stage's workspace batch.  *dst_out / *total_out: where the replayed batch is.
 int batchReplay(kx_program* p, uint32_t st, bool last, uint64_t nd, const uint8_t* cur, const unsigned long long* cur_off, const uint8_t* tok,
                 const unsigned long long* toff, unsigned long long tok_total, unsigned long long* stage_off, void* d_out, size_t cap, size_t* out_len,
-                unsigned long long nr, hipStream_t sm, BatchWs& W, kx_batch_stats& bst, uint8_t** dst_out, unsigned long long* total_out) {
+                unsigned long long nr, hipStream_t sm, BatchWs& W, kx_batch_stats& bst, uint8_t** dst_out, unsigned long long* total_out,
+                BFrame fr, const kx_batch_doc* rec, unsigned long long sfx8, uint32_t sfx) {   // fr: the frame of `cur`; sfx8, sfx: the suffix of every accepted document and its length (last stage)
   Stage& S = p->stages[st];
   const bool timing = p->cfg.collect_timing != 0;
   const uint32_t nregs = S.act_regs;
@@ -93,10 +100,10 @@ int batchReplay(kx_program* p, uint32_t st, bool last, uint64_t nd, const uint8_
   hipLaunchKernelGGL(k_bact_measure, dim3(mgrid), dim3(BACT_MT), 0, sm, tok, toff, (unsigned long long)nd, nregs, p->cfg.act_lanes, docs,
                      (uint32_t*)W.atab.p, (uint32_t*)W.awlist.p, (uint32_t*)W.adeep.p, actr);
   const uint32_t ng = (uint32_t)((nd + 1023) / 1024), g1024 = (uint32_t)((nd + 1 + 1023) / 1024);
-  hipLaunchKernelGGL(k_bscan_reduce, dim3(ng), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (unsigned long long*)W.wsum.p);
+  hipLaunchKernelGGL(k_bscan_reduce, dim3(ng), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (unsigned long long*)W.wsum.p, rec, (unsigned long long)sfx);
   hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, ng, (const unsigned long long*)W.wsum.p, (unsigned long long*)W.woff.p, (Flags*)W.flags.p);
   hipLaunchKernelGGL(k_bscan_down, dim3(g1024), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (const unsigned long long*)W.woff.p,
-                     (const Flags*)W.flags.p, stage_off);
+                     (const Flags*)W.flags.p, stage_off, rec, (unsigned long long)sfx);
   HIPCHECK(hipGetLastError());
   unsigned long long hc[BA_N] = {}, total = 0;
   HIPCHECK(hipMemcpyAsync(hc, actr, sizeof hc, hipMemcpyDeviceToHost, sm));
@@ -116,7 +123,7 @@ int batchReplay(kx_program* p, uint32_t st, bool last, uint64_t nd, const uint8_
       unsigned long long se[2];
       HIPCHECK(hipMemcpyAsync(se, cur_off + i, 16, hipMemcpyDeviceToHost, sm));
       HIPCHECK(hipStreamSynchronize(sm));
-      BRoute r{se[0], se[1] - se[0], i, 0, 0};
+      BRoute r{se[0], se[1] - se[0] - (i == fr.whole ? 0ull : fr.trim), i, 0, 0};
       int e = batchRouteOne(p, st, cur + r.start, r.len, sm, W, rpos, r);
       if (e) return e;
       routes.push_back(r);
@@ -158,6 +165,9 @@ int batchReplay(kx_program* p, uint32_t st, bool last, uint64_t nd, const uint8_
     }
     // the documents routed for their length hold their replayed output already
     if (nr) hipLaunchKernelGGL(k_bplace, dim3((uint32_t)nr), dim3(256), 0, sm, (const BRoute*)W.rres.p, (const uint8_t*)W.rout.p, (const unsigned long long*)stage_off, dst);
+    // the accepted documents' suffixes (inside actions_ms and total_ms; a retried document's k_bplace below stops before its suffix)
+    if (sfx) hipLaunchKernelGGL(k_bsuffix, dim3((uint32_t)((nd + 255) / 256)), dim3(256), 0, sm, (unsigned long long)nd, rec,
+                                (const unsigned long long*)stage_off, dst, sfx8, sfx);
   }
   if (timing) HIPCHECK(hipEventRecord(W.ev[9], sm));
   HIPCHECK(hipGetLastError());
@@ -194,9 +204,21 @@ struct DfSaved { uint32_t streak, skip; bool armed, given_up; int use_alt; };
 
 }  // namespace
 
-extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, void* d_out, size_t cap,
-                            uint64_t* d_out_off, kx_batch_doc* d_docs, size_t* out_len, kx_batch_stats* stats, void* stream) {
+namespace {
+
+// kx_run_batch (frame == nullptr) and kx_run_batch_framed
+int runBatch(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_frame* frame, void* d_out, size_t cap,
+             uint64_t* d_out_off, kx_batch_doc* d_docs, size_t* out_len, kx_batch_stats* stats, void* stream) {
   if (!p || !out_len) return setErr(KX_E_ARG, "null argument");
+  uint32_t trim = 0, sfx_len = 0;
+  bool last_whole = false;
+  unsigned long long sfx8 = 0;
+  if (frame) {
+    if (frame->suffix_len > 8) return setErr(KX_E_ARG, "kx_run_batch_framed: the suffix is at most 8 bytes");
+    for (uint32_t r : frame->reserved) if (r) return setErr(KX_E_ARG, "kx_run_batch_framed: reserved words must be 0");
+    trim = frame->trim; last_whole = frame->last_whole != 0; sfx_len = frame->suffix_len;
+    for (uint32_t i = 0; i < sfx_len; ++i) sfx8 |= (unsigned long long)frame->suffix[i] << (8 * i);
+  }
   if (n_docs && (!d_in_off || !d_out_off || !d_docs)) return setErr(KX_E_ARG, "kx_run_batch: offsets, output offsets and document records are required");
   if (n_docs >= 0xFFFFFFFFull) return setErr(KX_E_ARG, "kx_run_batch: at most 2^32 - 2 documents per call");
   *out_len = 0;
@@ -219,7 +241,9 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
     size_t lds = 0;
     for (auto& s : p->stages) lds = s.lds_bytes > lds ? s.lds_bytes : lds;
     for (const void* fn : {(const void*)k_bforward<false>, (const void*)k_bforward<true>, (const void*)k_bback<false>, (const void*)k_bback<true>,
-                           (const void*)k_bemit<false>, (const void*)k_bemit<true>}) {
+                           (const void*)k_bemit<false>, (const void*)k_bemit<true>,
+                           (const void*)k_bforward<false, BFrame>, (const void*)k_bforward<true, BFrame>, (const void*)k_bback<false, BFrame>,
+                           (const void*)k_bback<true, BFrame>, (const void*)k_bemit_fr<false, BFrame>, (const void*)k_bemit_fr<true, BFrame>}) {
       int rc = setLds(fn, lds);
       if (rc) return rc;
     }
@@ -253,7 +277,11 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
   unsigned long long* ctr = (unsigned long long*)W.ctr.p;
   HIPCHECK(hipMemsetAsync(ctr, 0, BC_N * 8, sm));
   // the offsets: non-decreasing, checked on the device before any kernel reads a document; the caller's records cleared
-  hipLaunchKernelGGL(k_bcheck, dim3((uint32_t)((nd + 255) / 256)), dim3(256), 0, sm, (const unsigned long long*)d_in_off, (unsigned long long)nd, d_docs, ctr);
+  // (a framed batch: also that no range is shorter than what the frame cuts from it)
+  const BFrame fr0{trim, trim && last_whole ? nd - 1 : BATCH_NO_WHOLE};
+  if (trim) hipLaunchKernelGGL(k_bcheck<BFrame>, dim3((uint32_t)((nd + 255) / 256)), dim3(256), 0, sm, (const unsigned long long*)d_in_off,
+                               (unsigned long long)nd, d_docs, ctr, fr0);
+  else hipLaunchKernelGGL(k_bcheck<>, dim3((uint32_t)((nd + 255) / 256)), dim3(256), 0, sm, (const unsigned long long*)d_in_off, (unsigned long long)nd, d_docs, ctr);
   HIPCHECK(hipGetLastError());
   unsigned long long hc[BC_N] = {0, 0, 0, 0}, ends[2] = {0, 0};
   HIPCHECK(hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, sm));
@@ -261,6 +289,7 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
   HIPCHECK(hipMemcpyAsync(&ends[1], d_in_off + nd, 8, hipMemcpyDeviceToHost, sm));
   HIPCHECK(hipStreamSynchronize(sm));
   if (hc[BC_BADOFF] || ends[1] < ends[0]) return setErr(KX_E_ARG, "kx_run_batch: the document offsets decrease");
+  if (hc[BC_SHORT]) return setErr(KX_E_ARG, "kx_run_batch_framed: a document's range is shorter than the trim");
   if (ends[1] > ends[0] && !d_in) return setErr(KX_E_ARG, "kx_run_batch: null input");
   bst.in_bytes = ends[1] - ends[0];
 
@@ -276,6 +305,9 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
     const bool wide = S.general;
     const bool replay = S.act && p->cfg.batch_actions == 2;   // the batch replay; else every document of an action stage is routed
     const size_t lds = S.lds_bytes;
+    const bool framed = st == 0 && trim != 0;                   // the <…, BFrame> instances: stage 0 of a batch with a trim
+    const BFrame fr = framed ? fr0 : BFrame{0, BATCH_NO_WHOLE};
+    const unsigned long long sfx = last ? sfx_len : 0;          // what the scan of the stage's OUTPUT lengths adds per accepted document
     const uint64_t nchk = (cur_bytes >> 5) + nd + 2, nslots = (cur_bytes >> 6) + nd;   // (k_bback writes every piece slot below nslots)
     rc = BatchWs::ensure(W.chk, nchk * 2);
     if (!rc) rc = BatchWs::ensure(W.brec, (nslots + 1) * sizeof(BRec));
@@ -288,8 +320,12 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
     // forward: lane = document
     HIPCHECK(hipMemsetAsync(ctr + BC_ROUTED, 0, 8, sm));
     if (timing) HIPCHECK(hipEventRecord(W.ev[0], sm));
-    hipLaunchKernelGGL(wide ? k_bforward<true> : k_bforward<false>, dim3(bgrid), dim3(BATCH_BT), lds, sm, cur, cur_off, (unsigned long long)nd,
-                       (unsigned long long)doc_max, S.act && !replay ? 1 : 0, st, (BDoc*)W.docs.p, d_docs, chk, (BRoute*)W.routes.p, ctr, S.T);
+    if (framed)
+      hipLaunchKernelGGL((wide ? k_bforward<true, BFrame> : k_bforward<false, BFrame>), dim3(bgrid), dim3(BATCH_BT), lds, sm, cur, cur_off, (unsigned long long)nd,
+                         (unsigned long long)doc_max, S.act && !replay ? 1 : 0, st, (BDoc*)W.docs.p, d_docs, chk, (BRoute*)W.routes.p, ctr, S.T, fr);
+    else
+      hipLaunchKernelGGL(wide ? k_bforward<true> : k_bforward<false>, dim3(bgrid), dim3(BATCH_BT), lds, sm, cur, cur_off, (unsigned long long)nd,
+                         (unsigned long long)doc_max, S.act && !replay ? 1 : 0, st, (BDoc*)W.docs.p, d_docs, chk, (BRoute*)W.routes.p, ctr, S.T);
     if (timing) HIPCHECK(hipEventRecord(W.ev[1], sm));
     HIPCHECK(hipGetLastError());
     unsigned long long nr = 0;
@@ -298,7 +334,11 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
     if (timing) bst.forward_ms += evMs(W.ev[0], W.ev[1]);
     // backward: lane = document
     if (timing) HIPCHECK(hipEventRecord(W.ev[2], sm));
-    hipLaunchKernelGGL(wide ? k_bback<true> : k_bback<false>, dim3(bgrid), dim3(BATCH_BT), lds, sm, cur, cur_off, (unsigned long long)nd, docs, chk, brec, S.T);
+    if (framed)
+      hipLaunchKernelGGL((wide ? k_bback<true, BFrame> : k_bback<false, BFrame>), dim3(bgrid), dim3(BATCH_BT), lds, sm, cur, cur_off, (unsigned long long)nd, docs,
+                         chk, brec, S.T, fr);
+    else
+      hipLaunchKernelGGL(wide ? k_bback<true> : k_bback<false>, dim3(bgrid), dim3(BATCH_BT), lds, sm, cur, cur_off, (unsigned long long)nd, docs, chk, brec, S.T);
     if (timing) HIPCHECK(hipEventRecord(W.ev[3], sm));
     HIPCHECK(hipGetLastError());
     // the routed documents, one at a time (in document order)
@@ -325,14 +365,15 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
     }
     // exclusive scan of the document lengths into `off` (off[nd] = the total, also left in Flags::total_len)
     const uint32_t ng = (uint32_t)((nd + 1023) / 1024);
-    auto scanDocs = [&](unsigned long long* off) {
-      hipLaunchKernelGGL(k_bscan_reduce, dim3(ng), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (unsigned long long*)W.wsum.p);
+    auto scanDocs = [&](unsigned long long* off, unsigned long long add) {
+      hipLaunchKernelGGL(k_bscan_reduce, dim3(ng), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (unsigned long long*)W.wsum.p,
+                         (const kx_batch_doc*)d_docs, add);
       hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, ng, (const unsigned long long*)W.wsum.p, (unsigned long long*)W.woff.p, (Flags*)W.flags.p);
       hipLaunchKernelGGL(k_bscan_down, dim3(g1024), dim3(1024), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (const unsigned long long*)W.woff.p,
-                         (const Flags*)W.flags.p, off);
+                         (const Flags*)W.flags.p, off, (const kx_batch_doc*)d_docs, add);
     };
     if (timing) HIPCHECK(hipEventRecord(W.ev[4], sm));
-    scanDocs(out_off);
+    scanDocs(out_off, replay ? 0 : sfx);   // (a replayed stage: these are the token streams' lengths; batchReplay's scan adds the suffix)
     if (timing) HIPCHECK(hipEventRecord(W.ev[5], sm));
     HIPCHECK(hipGetLastError());
     unsigned long long total = 0;
@@ -359,15 +400,23 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
     if (total) {
       hipLaunchKernelGGL(k_binit, dim3(bgrid), dim3(256), 0, sm, (unsigned long long)nd, (const BDoc*)docs, (const unsigned long long*)out_off, dst, S.T);
       const uint64_t eg = (nslots + BATCH_BT - 1) / BATCH_BT;
-      hipLaunchKernelGGL(wide ? k_bemit<true> : k_bemit<false>, dim3((uint32_t)(eg < bgrid ? eg : bgrid)), dim3(BATCH_BT), lds, sm, cur, cur_off,
-                         (unsigned long long)nslots, (const BDoc*)docs, (const uint16_t*)chk, (const BRec*)brec, (const unsigned long long*)out_off, dst, S.T);
+      if (framed)
+        hipLaunchKernelGGL((wide ? k_bemit_fr<true, BFrame> : k_bemit_fr<false, BFrame>), dim3((uint32_t)(eg < bgrid ? eg : bgrid)), dim3(BATCH_BT), lds, sm, cur, cur_off,
+                           (unsigned long long)nslots, (const BDoc*)docs, (const uint16_t*)chk, (const BRec*)brec, (const unsigned long long*)out_off, dst, S.T, fr);
+      else
+        hipLaunchKernelGGL(wide ? k_bemit<true> : k_bemit<false>, dim3((uint32_t)(eg < bgrid ? eg : bgrid)), dim3(BATCH_BT), lds, sm, cur, cur_off,
+                           (unsigned long long)nslots, (const BDoc*)docs, (const uint16_t*)chk, (const BRec*)brec, (const unsigned long long*)out_off, dst, S.T);
       // (a replayed stage's routed documents hold their REPLAYED output: placed behind the replay, below)
       if (nr && !replay) hipLaunchKernelGGL(k_bplace, dim3((uint32_t)nr), dim3(256), 0, sm, (const BRoute*)W.rres.p, (const uint8_t*)W.rout.p, (const unsigned long long*)out_off, dst);
+      // the accepted documents' suffixes (inside emit_ms and total_ms; a replayed stage's are written by batchReplay)
+      if (sfx && !replay) hipLaunchKernelGGL(k_bsuffix, dim3((uint32_t)((nd + 255) / 256)), dim3(256), 0, sm, (unsigned long long)nd, (const kx_batch_doc*)d_docs,
+                                             (const unsigned long long*)out_off, dst, sfx8, sfx_len);
     }
     if (timing) HIPCHECK(hipEventRecord(W.ev[7], sm));
     HIPCHECK(hipGetLastError());
     if (replay) {
-      rc = batchReplay(p, st, last, nd, cur, cur_off, (const uint8_t*)dst, out_off, total, stage_off, d_out, cap, out_len, nr, sm, W, bst, &dst, &total);
+      rc = batchReplay(p, st, last, nd, cur, cur_off, (const uint8_t*)dst, out_off, total, stage_off, d_out, cap, out_len, nr, sm, W, bst, &dst, &total,
+                       fr, (const kx_batch_doc*)d_docs, sfx8, (uint32_t)sfx);
       if (rc) break;
       out_off = stage_off;
     }
@@ -384,4 +433,17 @@ extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_i
   }
   if (stats) *stats = bst;
   return rc;
+}
+
+}  // namespace
+
+extern "C" int kx_run_batch(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, void* d_out, size_t cap,
+                            uint64_t* d_out_off, kx_batch_doc* d_docs, size_t* out_len, kx_batch_stats* stats, void* stream) {
+  return runBatch(p, d_in, d_in_off, n_docs, nullptr, d_out, cap, d_out_off, d_docs, out_len, stats, stream);
+}
+
+extern "C" int kx_run_batch_framed(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_frame* frame,
+                                   void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs, size_t* out_len, kx_batch_stats* stats,
+                                   void* stream) {
+  return runBatch(p, d_in, d_in_off, n_docs, frame, d_out, cap, d_out_off, d_docs, out_len, stats, stream);
 }

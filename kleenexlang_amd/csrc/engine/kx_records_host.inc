@@ -11,6 +11,12 @@
 // kx_split_records_rs, and the context it leaves (the last bytes of the unfinished record, fewer than the separator has) is the
 // context of the next window's split: a separator may straddle windows, and the carried record is then completed by a first
 // record that may be a single byte long.
+//
+// Framing (kx_run_records_fd_opts): with `chomp` every batch is a framed one (kx_run_batch_framed) whose trim is the separator's
+// length — the batch kernels run each record without its separator, no byte is moved — and with `ors` its suffix is the output
+// separator.  Only the stream's tail keeps its whole range: the last window's batch has last_whole = 1 when the split reported a
+// tail, and the carried record is left whole when it is that tail (the last window brought no separator).  The splitters know
+// nothing of this.
 
 namespace {
 
@@ -274,6 +280,9 @@ struct RecordsRun {
   uint32_t state = 0;                                  // at the start of the next window: bit 0 quote parity, bit 1 escaped
   uint8_t rs[8] = {}, ctx[8] = {};                     // the multi-byte separator (kx_run_records_fd_rs) and the next window's context
   uint32_t rs_len = 0, ctx_len = 0;                    // rs_len 0: a one-byte mode
+  bool chomp = false;                                  // records run without their separator
+  uint8_t ors[8] = {};                                 // what follows every accepted record's output
+  uint32_t ors_len = 0;
   RecQWs qws;
   RecEWs ews;
   RecRsWs rws;
@@ -306,16 +315,23 @@ struct RecordsRun {
   }
 
   // kx_run_batch of ndocs records (offsets d_o) into *out at byte pos; a buffer too small is replaced by one of the size needed,
-  // its first pos bytes kept.  Reports the rejected records (numbered from first_rec) and advances *pos.
-  int batch(const uint8_t* in, const uint64_t* d_o, uint64_t ndocs, DevBuf* out, size_t* pos, uint64_t first_rec) {
+  // its first pos bytes kept.  Reports the rejected records (numbered from first_rec) and advances *pos.  tail: the last of
+  // these records is the stream's tail (it has no separator to strip).
+  int batch(const uint8_t* in, const uint64_t* d_o, uint64_t ndocs, DevBuf* out, size_t* pos, uint64_t first_rec, bool tail) {
     if (ndocs == 0) return 0;
+    kx_batch_frame fr{};
+    fr.trim = chomp ? (rs_len ? rs_len : 1u) : 0u;
+    fr.last_whole = tail ? 1u : 0u;
+    fr.suffix_len = ors_len;
+    memcpy(fr.suffix, ors, ors_len);
+    const kx_batch_frame* frp = fr.trim || fr.suffix_len ? &fr : nullptr;
     int rc = BatchWs::ensure(ooff, (ndocs + 1) * 8);
     if (!rc) rc = BatchWs::ensure(docs, ndocs * sizeof(kx_batch_doc));
     if (rc) return rc;
     kx_batch_stats bs{};
     size_t ol = 0;
     if (timing) HIPCHECK(hipEventRecord(ev[2], nullptr));
-    rc = kx_run_batch(p, in, d_o, ndocs, out->d + *pos, out->cap - *pos, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, &ol, &bs, nullptr);
+    rc = kx_run_batch_framed(p, in, d_o, ndocs, frp, out->d + *pos, out->cap - *pos, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, &ol, &bs, nullptr);
     if (rc == KX_E_CAPACITY) {
       DevBuf nb;
       rc = fs->pool.get(*pos + ol + ol / 8 + 4096, &nb);
@@ -323,7 +339,7 @@ struct RecordsRun {
       if (*pos) HIPCHECK(hipMemcpy(nb.d, out->d, *pos, hipMemcpyDeviceToDevice));
       fs->pool.put(*out);
       *out = nb;
-      rc = kx_run_batch(p, in, d_o, ndocs, out->d + *pos, out->cap - *pos, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, &ol, &bs, nullptr);
+      rc = kx_run_batch_framed(p, in, d_o, ndocs, frp, out->d + *pos, out->cap - *pos, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, &ol, &bs, nullptr);
     }
     if (timing) { HIPCHECK(hipEventRecord(ev[3], nullptr)); HIPCHECK(hipEventSynchronize(ev[3])); st.batch_ms += evMs(ev[2], ev[3]); }
     if (rc != 0 && rc != KX_MATCH_ERROR) return rc;
@@ -404,7 +420,7 @@ struct RecordsRun {
       const uint64_t o2[2] = {0, carry_len};
       HIPCHECK(hipMemcpy(one.p, o2, 16, hipMemcpyHostToDevice));
       st.longest_record = carry_len > st.longest_record ? carry_len : st.longest_record;
-      rc = batch((const uint8_t*)carry.p, (const uint64_t*)one.p, 1, &out, &pos, recno + 1);
+      rc = batch((const uint8_t*)carry.p, (const uint64_t*)one.p, 1, &out, &pos, recno + 1, last && nsep == 0);   // (no separator ever came: the tail)
       if (rc) return rc;
       ++recno;
       carry_len = 0;
@@ -420,7 +436,7 @@ struct RecordsRun {
       hipLaunchKernelGGL(k_rlongest, dim3((uint32_t)(g < 1024 ? g : 1024)), dim3(256), 0, nullptr, (const unsigned long long*)(d_off + first),
                          (unsigned long long)nd, (unsigned long long*)longest.p);
       HIPCHECK(hipGetLastError());
-      rc = batch(in, d_off + first, nd, &out, &pos, recno + 1);
+      rc = batch(in, d_off + first, nd, &out, &pos, recno + 1, last && nrec > nsep);
       if (rc) return rc;
       recno += nd;
       uint64_t lr = 0;
@@ -529,7 +545,7 @@ namespace {
 // kx_run_records_fd (quote < 0, escape < 0), kx_run_records_fd_quoted (escape < 0), kx_run_records_fd_escaped and, with rs_len > 0,
 // kx_run_records_fd_rs (sep, quote and escape unused)
 int runRecordsFd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, int escape, int report_fd, kx_records_stats* stats,
-                 const uint8_t* rs = nullptr, uint32_t rs_len = 0) {
+                 const uint8_t* rs = nullptr, uint32_t rs_len = 0, bool chomp = false, const uint8_t* ors = nullptr, uint32_t ors_len = 0) {
   if (!p) return setErr(KX_E_ARG, "null argument");
   if (p->cfg.phase) return setErr(KX_E_ARG, "record mode runs every phase: kx_config::phase must be 0");
   const double t_begin = FdStream::nowMs();
@@ -544,6 +560,8 @@ int runRecordsFd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, i
   RecordsRun R;
   R.p = p; R.fs = &fsr; R.sep = sep; R.quote = quote; R.escape = escape; R.report_fd = report_fd;
   if (rs_len) { memcpy(R.rs, rs, rs_len); R.rs_len = rs_len; }
+  R.chomp = chomp;
+  if (ors_len) { memcpy(R.ors, ors, ors_len); R.ors_len = ors_len; }
   R.timing = p->cfg.collect_timing != 0;
   int rc = 0;
   if (R.timing) for (auto& e : R.ev) if (hipEventCreate(&e) != hipSuccess) rc = setErr(KX_E_HIP, "hipEventCreate failed");
@@ -589,4 +607,35 @@ extern "C" int kx_run_records_fd_rs(kx_program* p, int in_fd, int out_fd, const 
                                     kx_records_stats* stats) {
   if (!rs || rs_len < 1 || rs_len > 8) return setErr(KX_E_ARG, "kx_run_records_fd_rs: the separator must be 1 to 8 bytes");
   return runRecordsFd(p, in_fd, out_fd, 0, -1, -1, report_fd, stats, rs, rs_len);
+}
+
+extern "C" int kx_run_records_fd_opts(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, int report_fd, kx_records_stats* stats) {
+  if (!o) return setErr(KX_E_ARG, "null argument");
+  if (o->size != sizeof(kx_records_opts)) return setErr(KX_E_ARG, "kx_run_records_fd_opts: kx_records_opts::size is not this library's");
+  if (o->pad[0] || o->pad[1] || o->pad[2]) return setErr(KX_E_ARG, "kx_run_records_fd_opts: reserved words must be 0");
+  for (uint32_t r : o->reserved) if (r) return setErr(KX_E_ARG, "kx_run_records_fd_opts: reserved words must be 0");
+  if (o->ors_len > 8) return setErr(KX_E_ARG, "kx_run_records_fd_opts: the output separator is at most 8 bytes");
+  if (o->chomp > 1) return setErr(KX_E_ARG, "kx_run_records_fd_opts: chomp must be 0 or 1");
+  const bool chomp = o->chomp != 0;
+  const int sep = o->sep, quote = o->quote, escape = o->escape;
+  switch (o->mode) {
+    case KX_RECORDS_BYTE:
+      return runRecordsFd(p, in_fd, out_fd, o->sep, -1, -1, report_fd, stats, nullptr, 0, chomp, o->ors, o->ors_len);
+    case KX_RECORDS_QUOTED:
+      if (quote < 0 || quote > 255) return setErr(KX_E_ARG, "kx_run_records_fd_opts: quote must be a byte value");
+      if (quote == sep) return setErr(KX_E_ARG, "kx_run_records_fd_opts: the quote byte cannot be the separator");
+      return runRecordsFd(p, in_fd, out_fd, o->sep, quote, -1, report_fd, stats, nullptr, 0, chomp, o->ors, o->ors_len);
+    case KX_RECORDS_ESCAPED:
+      if (quote < -1 || quote > 255) return setErr(KX_E_ARG, "kx_run_records_fd_opts: quote must be a byte value or -1");
+      if (escape < 0 || escape > 255) return setErr(KX_E_ARG, "kx_run_records_fd_opts: escape must be a byte value");
+      if (quote == sep) return setErr(KX_E_ARG, "kx_run_records_fd_opts: the quote byte cannot be the separator");
+      if (escape == sep) return setErr(KX_E_ARG, "kx_run_records_fd_opts: the escape byte cannot be the separator");
+      if (quote == escape) return setErr(KX_E_ARG, "kx_run_records_fd_opts: the escape byte cannot be the quote byte");
+      return runRecordsFd(p, in_fd, out_fd, o->sep, quote, escape, report_fd, stats, nullptr, 0, chomp, o->ors, o->ors_len);
+    case KX_RECORDS_RS:
+      if (o->rs_len < 1 || o->rs_len > 8) return setErr(KX_E_ARG, "kx_run_records_fd_opts: the separator must be 1 to 8 bytes");
+      return runRecordsFd(p, in_fd, out_fd, 0, -1, -1, report_fd, stats, o->rs, o->rs_len, chomp, o->ors, o->ors_len);
+    default:
+      return setErr(KX_E_ARG, "kx_run_records_fd_opts: no such split mode");
+  }
 }

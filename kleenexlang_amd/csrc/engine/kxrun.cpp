@@ -14,7 +14,9 @@
 // `--quote[=Q]` (default a double quote) a separator inside Q-quoted fields ends no record (kx_run_records_fd_quoted).  With
 // `--escape[=E]` (default a backslash) a byte after an unescaped E is only data: never a separator, a quote or an escape
 // (kx_run_records_fd_escaped, with or without --quote).  With `--rs=STR` the separator is the 1 to 8 bytes STR spells, and records
-// end after its leftmost, non-overlapping copies (kx_run_records_fd_rs).
+// end after its leftmost, non-overlapping copies (kx_run_records_fd_rs).  With `--chomp` every record is run without its separator
+// (a last record without one is run whole), and with `--ors=STR` the 0 to 8 bytes STR spells follow the output of every accepted
+// record (kx_run_records_fd_opts): the framing is the command line's, the program sees only the record.
 //
 // BIN = this executable ++ KXP blob ++ libdir ++ trailer (see kexc main.cpp).
 // The engine is loaded with dlopen so that this file carries no HIP dependency.
@@ -75,6 +77,8 @@ static void usage(const char* name) {
   fprintf(stdout, "- \"%s --records[=SEP] --quote[=Q]\": the same, but a SEP inside Q-quoted fields (default Q: \") ends no record.\n", name);
   fprintf(stdout, "- \"%s --records[=SEP] [--quote[=Q]] --escape[=E]\": the same, but a byte after an unescaped E (default E: \\) is only data.\n", name);
   fprintf(stdout, "- \"%s --records --rs=STR\": records end after the 1 to 8 bytes STR spells (\\r\\n, \\n\\n, \\xHH ...), leftmost and non-overlapping.\n", name);
+  fprintf(stdout, "- \"%s --records ... --chomp\": every record is run without its separator (a last record without one is run whole).\n", name);
+  fprintf(stdout, "- \"%s --records ... --ors=STR\": the 0 to 8 bytes STR spells follow the output of every accepted record.\n", name);
 }
 
 // --records=SEP, --quote=Q, --escape=E: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
@@ -122,6 +126,12 @@ static bool parseSeparatorString(const char* a, uint8_t* rs, uint32_t* len) {
   return n >= 1;
 }
 
+// --ors=STR: as --rs, but 0 to 8 byte spellings (an empty STR: no output separator)
+static bool parseOutputSeparator(const char* a, uint8_t* ors, uint32_t* len) {
+  if (!*a) { *len = 0; return true; }
+  return parseSeparatorString(a, ors, len);
+}
+
 int main(int argc, char** argv) {
   // locate the payload appended to this executable
   FILE* self = fopen("/proc/self/exe", "rb");
@@ -144,10 +154,11 @@ int main(int argc, char** argv) {
 
   static struct option long_options[] = {{"phase", required_argument, 0, 'p'}, {"gpus", required_argument, 0, 'g'},
                                          {"records", optional_argument, 0, 'r'}, {"quote", optional_argument, 0, 'q'},
-                                         {"escape", optional_argument, 0, 'e'}, {"rs", required_argument, 0, 's'}, {0, 0, 0, 0}};
-  bool timing = false, records = false, quoted = false, escaped = false, sep_given = false, multi = false;
-  uint8_t sep = '\n', quote = '"', escape = '\\', rs[8] = {};
-  uint32_t rs_len = 0;
+                                         {"escape", optional_argument, 0, 'e'}, {"rs", required_argument, 0, 's'},
+                                         {"chomp", no_argument, 0, 'c'}, {"ors", required_argument, 0, 'o'}, {0, 0, 0, 0}};
+  bool timing = false, records = false, quoted = false, escaped = false, sep_given = false, multi = false, chomp = false, ors_given = false;
+  uint8_t sep = '\n', quote = '"', escape = '\\', rs[8] = {}, ors[8] = {};
+  uint32_t rs_len = 0, ors_len = 0;
   long phase = 0, gpus = 0;
   int c;
   while ((c = getopt_long(argc, argv, "ihtp:", long_options, nullptr)) != -1) {
@@ -180,6 +191,11 @@ int main(int argc, char** argv) {
         multi = true;
         if (!parseSeparatorString(optarg, rs, &rs_len)) { fprintf(stderr, "Invalid record separator: %s\n", optarg); return 1; }
         break;
+      case 'c': chomp = true; break;
+      case 'o':
+        ors_given = true;
+        if (!parseOutputSeparator(optarg, ors, &ors_len)) { fprintf(stderr, "Invalid output record separator: %s\n", optarg); return 1; }
+        break;
       case 'h':
       default: usage(argv[0]); return 1;
     }
@@ -195,6 +211,8 @@ int main(int argc, char** argv) {
   if (multi && !records) { fprintf(stderr, "%s: --rs needs --records\n", argv[0]); return 1; }
   if (multi && sep_given) { fprintf(stderr, "%s: --rs cannot be combined with --records=SEP\n", argv[0]); return 1; }
   if (multi && (quoted || escaped)) { fprintf(stderr, "%s: --rs cannot be combined with --quote or --escape\n", argv[0]); return 1; }
+  if (chomp && !records) { fprintf(stderr, "%s: --chomp needs --records\n", argv[0]); return 1; }
+  if (ors_given && !records) { fprintf(stderr, "%s: --ors needs --records\n", argv[0]); return 1; }
   struct timeval t0, t1;
   if (timing) gettimeofday(&t0, nullptr);
 
@@ -221,13 +239,30 @@ int main(int argc, char** argv) {
       runm = (decltype(runm))dlsym(h, "kx_run_records_fd_rs");
       if (!runm) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_rs (--rs needs a newer engine library)\n", argv[0]); return 1; }
     }
+    const bool framing = chomp || ors_len;   // (--ors= alone is the default: no output separator)
+    int (*runo)(kx_program*, int, int, const kx_records_opts*, int, kx_records_stats*) = nullptr;
+    if (framing) {
+      runo = (decltype(runo))dlsym(h, "kx_run_records_fd_opts");
+      if (!runo) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_opts (--chomp and --ors need a newer engine library)\n", argv[0]); return 1; }
+    }
     // record mode is where the single-document route is unusable (a third of a millisecond per record): stages with register
     // actions are replayed by the batch kernels unless KX_BATCH_ACTIONS=0 asks for the route
     if (!cfg.batch_actions) cfg.batch_actions = 2;
     kx_program* prog = nullptr;
     if (load(blob.data(), blob.size(), &cfg, &prog)) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 1; }
     kx_records_stats rs_stats;
-    if (multi) rc = runm(prog, STDIN_FILENO, STDOUT_FILENO, rs, rs_len, STDERR_FILENO, &rs_stats);
+    if (framing) {
+      kx_records_opts o{};
+      o.size = sizeof o;
+      o.mode = multi ? KX_RECORDS_RS : escaped ? KX_RECORDS_ESCAPED : quoted ? KX_RECORDS_QUOTED : KX_RECORDS_BYTE;
+      o.sep = sep;
+      o.quote = quoted ? (int)quote : -1;
+      o.escape = escaped ? (int)escape : -1;
+      memcpy(o.rs, rs, 8); o.rs_len = rs_len;
+      o.chomp = chomp ? 1u : 0u;
+      memcpy(o.ors, ors, 8); o.ors_len = ors_len;
+      rc = runo(prog, STDIN_FILENO, STDOUT_FILENO, &o, STDERR_FILENO, &rs_stats);
+    } else if (multi) rc = runm(prog, STDIN_FILENO, STDOUT_FILENO, rs, rs_len, STDERR_FILENO, &rs_stats);
     else if (escaped) rc = rune(prog, STDIN_FILENO, STDOUT_FILENO, sep, quoted ? (int)quote : -1, escape, STDERR_FILENO, &rs_stats);
     else rc = quoted ? runq(prog, STDIN_FILENO, STDOUT_FILENO, sep, quote, STDERR_FILENO, &rs_stats) : runr(prog, STDIN_FILENO, STDOUT_FILENO, sep, STDERR_FILENO, &rs_stats);
     if (rc != 0 && rc != KX_MATCH_ERROR) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 1; }

@@ -355,6 +355,68 @@ def split_rs_records_model(data, rs, ctx=b""):
     return offs, t[len(t) - min(m - 1, len(t)):], tail_len
 
 
+def _check_ors(ors):
+    """An output record separator: bytes of length 0 to 8 → bytes.  Raises TypeError / ValueError."""
+    if not isinstance(ors, (bytes, bytearray)):
+        raise TypeError("output record separator: bytes of length 0 to 8, not %s" % type(ors).__name__)
+    if len(ors) > 8:
+        raise ValueError("output record separator: 0 to 8 bytes, not %d" % len(ors))
+    return bytes(ors)
+
+
+def _check_chomp(chomp):
+    if not isinstance(chomp, bool):
+        raise TypeError("chomp: True or False, not %s" % type(chomp).__name__)
+    return chomp
+
+
+def _check_trim(trim):
+    """The trim of a framed batch: an int in [0, 2^32) → the int."""
+    if isinstance(trim, bool) or not isinstance(trim, int):
+        raise TypeError("trim: a non-negative int, not %s" % type(trim).__name__)
+    if not 0 <= trim < 1 << 32:
+        raise ValueError("trim: %d is not in [0, 2^32)" % trim)
+    return trim
+
+
+def chomp_records_model(data, offsets, trim, tail):
+    """kx_run_batch_framed's documents in pure Python — the normative model of `--chomp`: record i of `data` is
+    data[offsets[i]:offsets[i+1]] (a split model's offsets), and the document run for it is that range without its last `trim`
+    bytes (the separator: 1 byte, or len(rs)).  With `tail` the last record is the stream's tail — it has no valid separator,
+    whatever byte it ends in — and is run whole.  A record that is only its separator is the empty document.  Returns the list of
+    the documents' bytes.  Raises ValueError for a range shorter than `trim` (the engine's KX_E_ARG)."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError("chomp_records_model: data must be bytes, not %s" % type(data).__name__)
+    trim = _check_trim(trim)
+    if not isinstance(tail, bool):
+        raise TypeError("chomp_records_model: tail must be True or False, not %s" % type(tail).__name__)
+    data, offs = bytes(data), [int(o) for o in offsets]
+    check_batch_offsets(offs, len(data))
+    n, docs = len(offs) - 1, []
+    for i in range(n):
+        t = 0 if tail and i == n - 1 else trim
+        if offs[i + 1] - offs[i] < t:
+            raise ValueError("chomp_records_model: record %d is shorter than the trim (%d)" % (i, t))
+        docs.append(data[offs[i]:offs[i + 1] - t])
+    return docs
+
+
+class KxBatchFrame(ctypes.Structure):
+    """include/kxhip.h::kx_batch_frame."""
+    _fields_ = [("trim", ctypes.c_uint32), ("last_whole", ctypes.c_uint32), ("suffix_len", ctypes.c_uint32),
+                ("suffix", ctypes.c_uint8 * 8), ("reserved", ctypes.c_uint32 * 3)]
+
+
+KX_RECORDS_BYTE, KX_RECORDS_QUOTED, KX_RECORDS_ESCAPED, KX_RECORDS_RS = 0, 1, 2, 3
+
+
+class KxRecordsOpts(ctypes.Structure):
+    """include/kxhip.h::kx_records_opts."""
+    _fields_ = [("size", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("sep", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3),
+                ("quote", ctypes.c_int32), ("escape", ctypes.c_int32), ("rs", ctypes.c_uint8 * 8), ("rs_len", ctypes.c_uint32),
+                ("chomp", ctypes.c_uint32), ("ors", ctypes.c_uint8 * 8), ("ors_len", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
+
+
 def _check_values(values, what):
     import torch
     if not isinstance(values, torch.Tensor):
@@ -547,6 +609,10 @@ def load_engine():
         lib.kx_host_free.argtypes = [vp]
         lib.kx_run_fd.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxStats)]
         lib.kx_run_batch.argtypes = [vp, vp, vp, u64, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(KxBatchStats), vp]
+        lib.kx_run_batch_framed.argtypes = [vp, vp, vp, u64, ctypes.POINTER(KxBatchFrame), vp, sz, vp, vp, ctypes.POINTER(sz),
+                                            ctypes.POINTER(KxBatchStats), vp]
+        lib.kx_run_records_fd_opts.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.c_int,
+                                               ctypes.POINTER(KxRecordsStats)]
         lib.kx_split_records.argtypes = [vp, sz, ctypes.c_uint8, u64, vp, u64, ctypes.POINTER(u64), vp]
         lib.kx_run_records_fd.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.c_uint8, ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
         lib.kx_split_records_quoted.argtypes = [vp, sz, ctypes.c_uint8, ctypes.c_uint8, u32, u64, vp, u64, ctypes.POINTER(u64),
@@ -972,14 +1038,28 @@ class Program:
         ol = self.run_device(t.data_ptr(), n, out.data_ptr(), out.numel(), stream)
         return out[:ol]
 
-    def run_batch_tensor(self, values, offsets, out=None):
+    def run_batch_tensor(self, values, offsets, out=None, trim=0, last_whole=False, suffix=b""):
         """Batched run (kx_run_batch): document i is values[offsets[i]:offsets[i+1]], each a whole input of the program.
         values: CUDA uint8 tensor (any start address); offsets: int64 tensor of n_docs + 1 non-decreasing entries (on the
         device; a host tensor is checked here and copied).  Runs on the current stream; without `out` the output is sized
         by the capacity query (one more pass of everything but the placing).  Returns the device tensors
         (out_values, out_offsets, status, fail_pos, fail_stage): document i's output is out_values[out_offsets[i]:out_offsets[i+1]]
-        where status[i] == 0; status 1 = rejected at stage fail_stage[i], symbol fail_pos[i] (its range is empty)."""
+        where status[i] == 0; status 1 = rejected at stage fail_stage[i], symbol fail_pos[i] (its range is empty).
+        With `trim`, `last_whole` or `suffix` the batch is framed (kx_run_batch_framed): document i is
+        values[offsets[i]:offsets[i+1] - trim] (the last one whole with last_whole), and the 0 to 8 `suffix` bytes end the output
+        range of every accepted document (chomp_records_model)."""
         _check_batch_args(values, offsets)
+        trim = _check_trim(trim)
+        if not isinstance(last_whole, bool):
+            raise TypeError("run_batch_tensor: last_whole must be True or False, not %s" % type(last_whole).__name__)
+        if not isinstance(suffix, (bytes, bytearray)):
+            raise TypeError("run_batch_tensor: suffix must be bytes of length 0 to 8, not %s" % type(suffix).__name__)
+        if len(suffix) > 8:
+            raise ValueError("run_batch_tensor: suffix must be 0 to 8 bytes, not %d" % len(suffix))
+        frame = None
+        if trim or last_whole or suffix:
+            frame = KxBatchFrame(trim=trim, last_whole=1 if last_whole else 0, suffix_len=len(suffix))
+            frame.suffix[:len(suffix)] = bytes(suffix)
         import torch
         if not values.is_cuda:
             raise EngineError("run_batch_tensor: values must be on a HIP device (there is no CPU fallback)")
@@ -1000,10 +1080,17 @@ class Program:
         def call(buf):
             ol = ctypes.c_size_t()
             st = KxBatchStats()
-            rc = self._lib.kx_run_batch(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
-                                        ctypes.c_void_p(buf.data_ptr() if buf is not None and buf.numel() else None),
-                                        buf.numel() if buf is not None else 0, ctypes.c_void_p(out_off.data_ptr()),
-                                        ctypes.c_void_p(docs.data_ptr()), ctypes.byref(ol), ctypes.byref(st), ctypes.c_void_p(stream))
+            bptr = ctypes.c_void_p(buf.data_ptr() if buf is not None and buf.numel() else None)
+            bcap = buf.numel() if buf is not None else 0
+            if frame is None:
+                rc = self._lib.kx_run_batch(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n, bptr, bcap,
+                                            ctypes.c_void_p(out_off.data_ptr()), ctypes.c_void_p(docs.data_ptr()), ctypes.byref(ol),
+                                            ctypes.byref(st), ctypes.c_void_p(stream))
+            else:
+                rc = self._lib.kx_run_batch_framed(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
+                                                   ctypes.byref(frame), bptr, bcap, ctypes.c_void_p(out_off.data_ptr()),
+                                                   ctypes.c_void_p(docs.data_ptr()), ctypes.byref(ol), ctypes.byref(st),
+                                                   ctypes.c_void_p(stream))
             self.last_batch_stats = st
             return rc, ol.value
 
@@ -1070,16 +1157,19 @@ class Program:
             raise ValueError("%s: rs= cannot be combined with quote= or escape=" % what)
         return rs
 
-    def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None, batch_actions=True, rs=None):
+    def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None, batch_actions=True, rs=None, chomp=False, ors=b""):
         """Record mode on bytes: every record of `data` (split after each `sep` byte, kx_split_records on the device) is a
         whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage).  With a `quote` byte
         a separator inside quotes ends no record (kx_split_records_quoted from parity 0).  With an `escape` byte an escaped
         byte is only data (kx_split_records_escaped from state 0).  `batch_actions`: stages with register actions are replayed
         by the batch kernels (kx_config::batch_actions = 2 for this call) instead of routing every record.  With `rs` (1 to 8
         bytes; not with a `sep`, `quote` or `escape`) records end after the leftmost, non-overlapping copies of rs
-        (kx_split_records_rs from an empty context)."""
+        (kx_split_records_rs from an empty context).  With `chomp` every record is run without its separator (a tail, which
+        has no valid one, whole) and the 0 to 8 bytes `ors` end the output of every accepted record (kx_run_batch_framed,
+        chomp_records_model)."""
         if not isinstance(data, (bytes, bytearray, memoryview)):
             raise TypeError("run_records: data must be bytes, not %s" % type(data).__name__)
+        chomp, ors = _check_chomp(chomp), _check_ors(ors)
         if rs is not None:
             rs = self._check_rs_alone(rs, sep, quote, escape, "run_records")
         _check_sep(sep)
@@ -1092,24 +1182,40 @@ class Program:
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         v = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else torch.empty(0, dtype=torch.uint8, device=dev)
         if rs is not None:
-            offs = split_rs_records_tensor(v, rs)[0]
-        elif escape is not None:
-            offs = split_escaped_records_tensor(v, sep, quote, escape)[0]
+            offs, (_, tail_len) = split_rs_records_tensor(v, rs)
+            tail = tail_len > 0                          # (the splitter's own report)
         else:
-            offs = split_records_tensor(v, sep) if quote is None else split_quoted_records_tensor(v, sep, quote)[0]
+            if escape is not None:
+                offs, _ = split_escaped_records_tensor(v, sep, quote, escape)
+                model = lambda d: split_escaped_records_model(d, sep, quote, escape)[0]   # noqa: E731
+            elif quote is not None:
+                offs, _ = split_quoted_records_tensor(v, sep, quote)
+                model = lambda d: split_records_model(d, sep, quote)                      # noqa: E731
+            else:
+                offs = split_records_tensor(v, sep)
+                model = lambda d: split_records_model(d, sep)                             # noqa: E731
+            # tail: the last record has no valid separator.  The record starts at a boundary, where the split's state is 0, so
+            # the split model says it: with one more byte behind the record, its end is a boundary iff a separator ends it.
+            # (`data` is bytes here, whatever came in; reading offs[-2] waits for the split, as the batch's size query would.)
+            last = data[int(offs[-2]):] if chomp and offs.numel() > 1 else b""
+            tail = bool(last) and len(last) not in model(last + b"\0")[:-1]
+        trim = (len(rs) if rs is not None else 1) if chomp else 0
         with self._batch_actions_for_call(batch_actions):
-            out, ooff, status, fpos, fstage = self.run_batch_tensor(v, offs)
+            out, ooff, status, fpos, fstage = self.run_batch_tensor(v, offs, trim=trim, last_whole=bool(trim and tail and data), suffix=ors)
         torch.cuda.synchronize(dev)
         ob = out.cpu().numpy().tobytes()
         ooff, status, fpos, fstage = ooff.tolist(), status.tolist(), fpos.tolist(), fstage.tolist()
         return [MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]] for i in range(len(status))]
 
-    def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None, batch_actions=True, rs=None):
+    def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None, batch_actions=True, rs=None, chomp=False,
+                       ors=b""):
         """kx_run_records_fd: the stream on in_fd in record mode, outputs to out_fd, one line per rejected record to report_fd
         (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected.  With a `quote`
         byte, kx_run_records_fd_quoted: a separator inside quotes ends no record.  With an `escape` byte,
         kx_run_records_fd_escaped: an escaped byte is only data (with or without a quote).  With `rs` (1 to 8 bytes),
-        kx_run_records_fd_rs: records end after the leftmost, non-overlapping copies of rs.  `batch_actions` as in run_records."""
+        kx_run_records_fd_rs: records end after the leftmost, non-overlapping copies of rs.  `batch_actions` as in run_records.  With
+        `chomp` or a non-empty `ors`, kx_run_records_fd_opts: records run without their separator, `ors` after every accepted
+        record's output."""
         for name, fd in (("in_fd", in_fd), ("out_fd", out_fd), ("report_fd", report_fd)):
             if isinstance(fd, bool) or not isinstance(fd, int):
                 raise TypeError("run_records_fd: %s must be an int file descriptor, not %s" % (name, type(fd).__name__))
@@ -1118,9 +1224,20 @@ class Program:
         s = _check_sep(sep)
         q = None if quote is None else _check_quote(quote, sep)
         e = None if escape is None else _check_escape(escape, sep, quote)
+        chomp, ors = _check_chomp(chomp), _check_ors(ors)
         st = KxRecordsStats()
         with self._batch_actions_for_call(batch_actions):
-            if rs is not None:
+            if chomp or ors:
+                o = KxRecordsOpts(size=ctypes.sizeof(KxRecordsOpts), sep=s, quote=-1 if q is None else q, escape=-1 if e is None else e,
+                                  chomp=1 if chomp else 0, ors_len=len(ors))
+                o.mode = KX_RECORDS_RS if rs is not None else KX_RECORDS_ESCAPED if e is not None else \
+                    KX_RECORDS_QUOTED if q is not None else KX_RECORDS_BYTE
+                if rs is not None:
+                    o.rs[:len(rs)] = rs
+                    o.rs_len = len(rs)
+                o.ors[:len(ors)] = ors
+                rc = self._lib.kx_run_records_fd_opts(self._h, in_fd, out_fd, ctypes.byref(o), report_fd, ctypes.byref(st))
+            elif rs is not None:
                 rc = self._lib.kx_run_records_fd_rs(self._h, in_fd, out_fd, rs, len(rs), report_fd, ctypes.byref(st))
             elif e is not None:
                 rc = self._lib.kx_run_records_fd_escaped(self._h, in_fd, out_fd, s, -1 if q is None else q, e, report_fd, ctypes.byref(st))
