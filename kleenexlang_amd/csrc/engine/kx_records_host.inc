@@ -1,16 +1,19 @@
-// kx_records_host.inc — host side of record mode (include/kxhip.h: kx_split_records, kx_run_records_fd; kernels in
-// kx_records.inc).  Included at the end of kx_engine.hip, behind kx_batch_host.inc.
+// kx_records_host.inc — host side of record mode (include/kxhip.h: kx_split_records*, kx_run_records_fd*; kernels in
+// kx_records.inc, kx_records_quoted.inc, kx_records_escaped.inc, kx_records_rs.inc).  Included at the end of kx_engine.hip, behind
+// kx_batch_host.inc.
 //
-// kx_run_records_fd reuses FdStream's reader and writer threads and its buffer pool (kx_run_fd); only the compute step differs.
-// Windows are independent: per window, kx_split_records → kx_run_batch over the complete records → one output window → one
-// report line per rejected record.  The record that straddles a window's end is carried (device memory, grown as needed) and
-// run as a one-document batch in front of the next window's records.  With a quote byte (kx_run_records_fd_quoted) the split is
-// kx_split_records_quoted, and the quote parity at the end of each window is the parity_in of the next; nothing else differs.
-// With an escape byte (kx_run_records_fd_escaped) the split is kx_split_records_escaped, and the state it ends in (quote parity,
-// escape) is the state_in of the next window's split.  With a multi-byte separator (kx_run_records_fd_rs) the split is
-// kx_split_records_rs, and the context it leaves (the last bytes of the unfinished record, fewer than the separator has) is the
-// context of the next window's split: a separator may straddle windows, and the carried record is then completed by a first
-// record that may be a single byte long.
+// A split is described once: a SplitSpec (the mode and its bytes) and a SplitCarry (what a buffer hands the one behind it: the
+// quote parity and escape state, or the context of a multi-byte separator).  checkSplit is the one place that knows which are
+// allowed; every entry point calls it.  splitRecords is the one driver: the empty buffer, the alignment, the workspace, the total's
+// read-back, the capacity refusal and the final sync are its own; per mode it has the kernels that count, the tail decision with
+// the outgoing carry, and the kernel that writes.  One flat RecWs holds every mode's buffers; a mode grows the ones it uses.
+//
+// kx_run_records_fd* reuse FdStream's reader and writer threads and its buffer pool (kx_run_fd); only the compute step differs.
+// Windows are independent: per window, the split → kx_run_batch over the complete records → one output window → one report line
+// per rejected record.  The record that straddles a window's end is carried (device memory, grown as needed) and run as a
+// one-document batch in front of the next window's records.  The SplitCarry a window's split ends in is the next window's: quotes,
+// an escape or a multi-byte separator may straddle windows, and with the last the carried record is completed by a first record
+// that may be a single byte long.
 //
 // Framing (kx_run_records_fd_opts): with `chomp` every batch is a framed one (kx_run_batch_framed) whose trim is the separator's
 // length — the batch kernels run each record without its separator, no byte is moved — and with `ors` its suffix is the output
@@ -20,167 +23,53 @@
 
 namespace {
 
-struct RecWs {   // grow-only device workspace of a split (tile counts, their offsets, the scan's Flags)
-  BatchWs::Buf tcount, toff, flags;
-  ~RecWs() { for (BatchWs::Buf* b : {&tcount, &toff, &flags}) if (b->p) (void)hipFree(b->p); }
+// which split, with which bytes: a split reads the front part of kx_records_opts, and of that only its mode's fields (sep: BYTE,
+// QUOTED, ESCAPED; quote: QUOTED, and ESCAPED, where -1 is none; escape: ESCAPED; rs, rs_len: RS)
+typedef kx_records_opts SplitSpec;
+
+struct SplitCarry {   // what a buffer hands the one behind it
+  uint32_t state = 0;    // QUOTED, ESCAPED: bit 0 the quote parity, bit 1 the next byte is escaped
+  uint8_t ctx[8] = {};   // RS: the last bytes of the unfinished record, fewer than rs has
+  uint32_t ctx_len = 0;
 };
 
-// the split; *nsep = separators in the buffer, *nrec = records (nsep, or nsep + 1 with a non-empty tail)
-int splitRecords(const uint8_t* d_in, size_t n, uint8_t sep, uint64_t base, uint64_t* d_off, uint64_t cap, uint64_t* nrec,
-                 uint64_t* nsep, RecWs& W, hipStream_t sm) {
-  *nrec = 0; *nsep = 0;
-  if (n == 0) {
-    if (cap < 1) return setErr(KX_E_CAPACITY, "kx_split_records: offsets buffer too small");
-    HIPCHECK(hipMemcpyAsync(d_off, &base, 8, hipMemcpyHostToDevice, sm));
-    HIPCHECK(hipStreamSynchronize(sm));
-    return 0;
+// the rules of every record entry point (`who`): KX_E_ARG unless splitRecords can run this spec from this carry
+int checkSplit(const SplitSpec& s, const SplitCarry& in, const char* who) {
+  auto no = [&](const char* what) { return setErr(KX_E_ARG, std::string(who) + ": " + what); };
+  switch (s.mode) {
+    case KX_RECORDS_BYTE:
+      return 0;
+    case KX_RECORDS_QUOTED:
+      if (s.quote < 0 || s.quote > 255) return no("quote must be a byte value");
+      if (s.quote == s.sep) return no("the quote byte cannot be the separator");
+      if (in.state > 1) return no("parity_in must be 0 or 1");
+      return 0;
+    case KX_RECORDS_ESCAPED:
+      if (s.quote < -1 || s.quote > 255) return no("quote must be a byte value or -1");
+      if (s.escape < 0 || s.escape > 255) return no("escape must be a byte value");
+      if (s.quote == s.sep) return no("the quote byte cannot be the separator");
+      if (s.escape == s.sep) return no("the escape byte cannot be the separator");
+      if (s.quote == s.escape) return no("the escape byte cannot be the quote byte");
+      if (in.state > 3 || (s.quote < 0 && (in.state & 1u))) return no("state_in must be 0-3, bit 0 only with a quote");
+      return 0;
+    case KX_RECORDS_RS:
+      if (s.rs_len < 1 || s.rs_len > 8) return no("the separator must be 1 to 8 bytes");
+      if (in.ctx_len >= s.rs_len) return no("the context must be shorter than the separator");
+      return 0;
+    default:
+      return no("no such split mode");
   }
-  const uint8_t* a0 = (const uint8_t*)((uintptr_t)d_in & ~(uintptr_t)15);
-  const unsigned long long lo = (unsigned long long)(d_in - a0), hi = lo + n, ng = (hi + 15) / 16;
-  const unsigned long long ntiles = (ng + REC_TILE - 1) / REC_TILE;
-  if (ntiles > 0x7FFFFFFFull) return setErr(KX_E_ARG, "kx_split_records: buffer too large");
-  int rc = BatchWs::ensure(W.tcount, ntiles * 8);
-  if (!rc) rc = BatchWs::ensure(W.toff, ntiles * 8);
-  if (!rc) rc = BatchWs::ensure(W.flags, sizeof(Flags));
-  if (rc) return rc;
-  const uint32_t pat = 0x01010101u * sep;
-  hipLaunchKernelGGL(k_rcount, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, pat, (unsigned long long*)W.tcount.p);
-  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, (const unsigned long long*)W.tcount.p,
-                     (unsigned long long*)W.toff.p, (Flags*)W.flags.p);
-  HIPCHECK(hipGetLastError());
-  unsigned long long total = 0;
-  uint8_t lastb = 0;
-  HIPCHECK(hipMemcpyAsync(&total, &((Flags*)W.flags.p)->total_len, 8, hipMemcpyDeviceToHost, sm));
-  HIPCHECK(hipMemcpyAsync(&lastb, d_in + n - 1, 1, hipMemcpyDeviceToHost, sm));
-  HIPCHECK(hipStreamSynchronize(sm));
-  const int tail = lastb != sep;
-  *nsep = total;
-  *nrec = total + (uint64_t)tail;
-  if (cap < *nrec + 1 || !d_off) return setErr(KX_E_CAPACITY, "kx_split_records: offsets buffer too small");
-  hipLaunchKernelGGL(k_rwrite, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, pat, (const unsigned long long*)W.toff.p,
-                     (unsigned long long)base, total, tail, (unsigned long long*)d_off);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipStreamSynchronize(sm));
-  return 0;
 }
 
-struct RecQWs {   // grow-only device workspace of a quoted split: RecWs (tcount = the selected counts) plus the per-tile quote counts,
-                  // their scan, the separators and the separators outside quotes from an even start; flags holds two Flags
-  RecWs base;
-  BatchWs::Buf tq, tqoff, tsep, teven;
-  ~RecQWs() { for (BatchWs::Buf* b : {&tq, &tqoff, &tsep, &teven}) if (b->p) (void)hipFree(b->p); }
-};
-
-// the quoted split (quote != sep, parity_in ≤ 1); *nsep = separators outside quotes, *nrec = records, *parity_out = parity_in ^ the
-// quote count's parity
-int splitRecordsQuoted(const uint8_t* d_in, size_t n, uint8_t sep, uint8_t quote, uint32_t parity_in, uint64_t base, uint64_t* d_off,
-                       uint64_t cap, uint64_t* nrec, uint64_t* nsep, uint32_t* parity_out, RecQWs& W, hipStream_t sm) {
-  *nrec = 0; *nsep = 0; *parity_out = parity_in;
-  if (n == 0) {
-    if (cap < 1) return setErr(KX_E_CAPACITY, "kx_split_records_quoted: offsets buffer too small");
-    HIPCHECK(hipMemcpyAsync(d_off, &base, 8, hipMemcpyHostToDevice, sm));
-    HIPCHECK(hipStreamSynchronize(sm));
-    return 0;
+struct RecWs {   // grow-only device workspace of a split; a mode grows only the buffers it uses
+  BatchWs::Buf tcount, toff, flags;     // every mode: the selected separators per tile, their scan, the scans' Flags (two with quotes)
+  BatchWs::Buf tq, tqoff, tsep, teven;  // QUOTED, ESCAPED: per tile the quotes, their scan, the separators, those outside quotes from an even start
+  BatchWs::Buf tflag;                   // ESCAPED: the per-tile flag words
+  BatchWs::Buf tmap, tcnt;              // RS with overlapping copies: the per-tile maps / states, the counts per state
+  BatchWs::Buf info;                    // ESCAPED, overlapping RS: the info word (how the buffer ends)
+  ~RecWs() {
+    for (BatchWs::Buf* b : {&tcount, &toff, &flags, &tq, &tqoff, &tsep, &teven, &tflag, &tmap, &tcnt, &info}) if (b->p) (void)hipFree(b->p);
   }
-  const uint8_t* a0 = (const uint8_t*)((uintptr_t)d_in & ~(uintptr_t)15);
-  const unsigned long long lo = (unsigned long long)(d_in - a0), hi = lo + n, ng = (hi + 15) / 16;
-  const unsigned long long ntiles = (ng + REC_TILE - 1) / REC_TILE;
-  if (ntiles > 0x7FFFFFFFull) return setErr(KX_E_ARG, "kx_split_records_quoted: buffer too large");
-  int rc = 0;
-  for (BatchWs::Buf* b : {&W.base.tcount, &W.base.toff, &W.tq, &W.tqoff, &W.tsep, &W.teven}) if (!rc) rc = BatchWs::ensure(*b, ntiles * 8);
-  if (!rc) rc = BatchWs::ensure(W.base.flags, 2 * sizeof(Flags));
-  if (rc) return rc;
-  const uint32_t spat = 0x01010101u * sep, qpat = 0x01010101u * quote;
-  auto U = [](BatchWs::Buf& b) { return (unsigned long long*)b.p; };
-  Flags* fl = (Flags*)W.base.flags.p;
-  hipLaunchKernelGGL(k_rqcount, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, qpat, U(W.tq), U(W.tsep), U(W.teven));
-  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, (const unsigned long long*)W.tq.p, U(W.tqoff), fl);
-  hipLaunchKernelGGL(k_rqselect, dim3((uint32_t)((ntiles + 255) / 256)), dim3(256), 0, sm, (uint32_t)ntiles, (const unsigned long long*)W.tqoff.p,
-                     (const unsigned long long*)W.tsep.p, (const unsigned long long*)W.teven.p, parity_in, U(W.base.tcount));
-  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, (const unsigned long long*)W.base.tcount.p, U(W.base.toff),
-                     fl + 1);
-  HIPCHECK(hipGetLastError());
-  unsigned long long quotes = 0, total = 0;
-  uint8_t lastb = 0;
-  HIPCHECK(hipMemcpyAsync(&quotes, &fl[0].total_len, 8, hipMemcpyDeviceToHost, sm));
-  HIPCHECK(hipMemcpyAsync(&total, &fl[1].total_len, 8, hipMemcpyDeviceToHost, sm));
-  HIPCHECK(hipMemcpyAsync(&lastb, d_in + n - 1, 1, hipMemcpyDeviceToHost, sm));
-  HIPCHECK(hipStreamSynchronize(sm));
-  *parity_out = parity_in ^ (uint32_t)(quotes & 1u);
-  const int tail = !(lastb == sep && *parity_out == 0);   // (a last separator byte inside quotes ends no record)
-  *nsep = total;
-  *nrec = total + (uint64_t)tail;
-  if (cap < *nrec + 1 || !d_off) return setErr(KX_E_CAPACITY, "kx_split_records_quoted: offsets buffer too small");
-  hipLaunchKernelGGL(k_rqwrite, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, qpat, (const unsigned long long*)W.tqoff.p,
-                     parity_in, (const unsigned long long*)W.base.toff.p, (unsigned long long)base, total, tail, (unsigned long long*)d_off);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipStreamSynchronize(sm));
-  return 0;
-}
-
-struct RecEWs {   // grow-only device workspace of an escaped split: RecQWs plus the per-tile flag words and the info word
-  RecQWs q;
-  BatchWs::Buf tflag, info;
-  ~RecEWs() { for (BatchWs::Buf* b : {&tflag, &info}) if (b->p) (void)hipFree(b->p); }
-};
-
-// the escaped split (escape != sep, escape != quote, quote != sep; quote < 0: none; state_in ≤ 3, bit 0 only with a quote);
-// *nsep = valid separators, *nrec = records, *state_out = the quote parity (bit 0) and the escape state (bit 1) after the buffer
-int splitRecordsEscaped(const uint8_t* d_in, size_t n, uint8_t sep, int quote, uint8_t escape, uint32_t state_in, uint64_t base,
-                        uint64_t* d_off, uint64_t cap, uint64_t* nrec, uint64_t* nsep, uint32_t* state_out, RecEWs& W, hipStream_t sm) {
-  *nrec = 0; *nsep = 0; *state_out = state_in;
-  if (n == 0) {
-    if (cap < 1) return setErr(KX_E_CAPACITY, "kx_split_records_escaped: offsets buffer too small");
-    HIPCHECK(hipMemcpyAsync(d_off, &base, 8, hipMemcpyHostToDevice, sm));
-    HIPCHECK(hipStreamSynchronize(sm));
-    return 0;
-  }
-  const uint8_t* a0 = (const uint8_t*)((uintptr_t)d_in & ~(uintptr_t)15);
-  const unsigned long long lo = (unsigned long long)(d_in - a0), hi = lo + n, ng = (hi + 15) / 16;
-  const unsigned long long ntiles = (ng + REC_TILE - 1) / REC_TILE;
-  if (ntiles > 0x7FFFFFFFull) return setErr(KX_E_ARG, "kx_split_records_escaped: buffer too large");
-  RecQWs& Q = W.q;
-  int rc = 0;
-  for (BatchWs::Buf* b : {&Q.base.tcount, &Q.base.toff, &Q.tq, &Q.tqoff, &Q.tsep, &Q.teven}) if (!rc) rc = BatchWs::ensure(*b, ntiles * 8);
-  if (!rc) rc = BatchWs::ensure(Q.base.flags, 2 * sizeof(Flags));
-  if (!rc) rc = BatchWs::ensure(W.tflag, ntiles * 4);
-  if (!rc) rc = BatchWs::ensure(W.info, 4);
-  if (rc) return rc;
-  const uint32_t spat = 0x01010101u * sep, qpat = 0x01010101u * (uint8_t)(quote < 0 ? 0 : quote), epat = 0x01010101u * escape;
-  const uint32_t qkeep = quote < 0 ? 0u : 0xFFFF0000u, x = state_in >> 1, parity_in = state_in & 1u;
-  auto U = [](BatchWs::Buf& b) { return (unsigned long long*)b.p; };
-  auto C = [](BatchWs::Buf& b) { return (const unsigned long long*)b.p; };
-  Flags* fl = (Flags*)Q.base.flags.p;
-  uint32_t* tflag = (uint32_t*)W.tflag.p;
-  hipLaunchKernelGGL(k_recount, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, qpat, qkeep, epat, x, U(Q.tq), U(Q.tsep),
-                     U(Q.teven), tflag);
-  hipLaunchKernelGGL(k_rescan, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, lo == 0 ? x : 0u, tflag, U(Q.tq));
-  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, C(Q.tq), U(Q.tqoff), fl);
-  hipLaunchKernelGGL(k_reselect, dim3((uint32_t)((ntiles + 255) / 256)), dim3(256), 0, sm, (uint32_t)ntiles, (const uint32_t*)tflag, C(Q.tq),
-                     C(Q.tqoff), C(Q.tsep), C(Q.teven), parity_in, U(Q.base.tcount), (uint32_t*)W.info.p);
-  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, C(Q.base.tcount), U(Q.base.toff), fl + 1);
-  HIPCHECK(hipGetLastError());
-  unsigned long long total = 0;
-  uint32_t info = 0;
-  HIPCHECK(hipMemcpyAsync(&total, &fl[1].total_len, 8, hipMemcpyDeviceToHost, sm));
-  HIPCHECK(hipMemcpyAsync(&info, W.info.p, 4, hipMemcpyDeviceToHost, sm));
-  HIPCHECK(hipStreamSynchronize(sm));
-  *state_out = (info >> 1) & 3u;
-  const int tail = !(info & 1u);   // (an escaped separator, or one inside quotes, as the last byte ends no record)
-  *nsep = total;
-  *nrec = total + (uint64_t)tail;
-  if (cap < *nrec + 1 || !d_off) return setErr(KX_E_CAPACITY, "kx_split_records_escaped: offsets buffer too small");
-  hipLaunchKernelGGL(k_rewrite, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, qpat, qkeep, epat, x, (const uint32_t*)tflag,
-                     C(Q.tqoff), parity_in, C(Q.base.toff), (unsigned long long)base, total, tail, (unsigned long long*)d_off);
-  HIPCHECK(hipGetLastError());
-  HIPCHECK(hipStreamSynchronize(sm));
-  return 0;
-}
-
-struct RecRsWs {   // grow-only device workspace of a multi-byte split: RecWs plus the per-tile maps / states, counts per state, info
-  RecWs base;
-  BatchWs::Buf tmap, tcnt, info;
-  ~RecRsWs() { for (BatchWs::Buf* b : {&tmap, &tcnt, &info}) if (b->p) (void)hipFree(b->p); }
 };
 
 // no proper prefix of rs is also a suffix: copies of rs cannot overlap
@@ -189,103 +78,159 @@ bool rsBorderFree(const uint8_t* rs, uint32_t m) {
   return true;
 }
 
-// the multi-byte split (1 ≤ m ≤ 8, k < m; rs, ctx, ctx_out host memory); *nsep = selected separators, *nrec = records.  On
-// success *ctx_out_len bytes of ctx_out (7 bytes) = the context for the buffer behind this one and *tail_len = the bytes of this
-// buffer behind its last selected separator (host.split_rs_records_model).
-int splitRecordsRs(const uint8_t* d_in, size_t n, const uint8_t* rs, uint32_t m, const uint8_t* ctx, uint32_t k, uint64_t base,
-                   uint64_t* d_off, uint64_t cap, uint64_t* nrec, uint64_t* nsep, uint8_t* ctx_out, uint32_t* ctx_out_len, uint64_t* tail_len,
-                   RecRsWs& W, hipStream_t sm) {
-  *nrec = 0; *nsep = 0;
+// the split of d_in[0, n) (checkSplit has passed): *nsep = selected separators, *nrec = records (nsep, or nsep + 1 with a
+// non-empty tail), d_off[0 .. *nrec] their offsets from base.  *out = the carry for the buffer behind this one: its state is set
+// on 0 and on KX_E_CAPACITY, its context and *tail_len (RS: the bytes of this buffer behind its last selected separator,
+// host.split_rs_records_model) only on 0.  KX_E_CAPACITY (cap < *nrec + 1) writes nothing to d_off.
+int splitRecords(const SplitSpec& s, const SplitCarry in, const uint8_t* d_in, size_t n, uint64_t base, uint64_t* d_off, uint64_t cap,
+                 uint64_t* nrec, uint64_t* nsep, SplitCarry* out, uint64_t* tail_len, RecWs& W, hipStream_t sm) {
+  static const char* const name[4] = {"kx_split_records", "kx_split_records_quoted", "kx_split_records_escaped", "kx_split_records_rs"};
+  auto err = [&](int code, const char* what) { return setErr(code, std::string(name[s.mode]) + ": " + what); };
+  *nrec = 0; *nsep = 0; *out = in; *tail_len = 0;
   if (n == 0) {
-    if (cap < 1) return setErr(KX_E_CAPACITY, "kx_split_records_rs: offsets buffer too small");
+    if (cap < 1) return err(KX_E_CAPACITY, "offsets buffer too small");
     HIPCHECK(hipMemcpyAsync(d_off, &base, 8, hipMemcpyHostToDevice, sm));
     HIPCHECK(hipStreamSynchronize(sm));
-    memmove(ctx_out, ctx, k);
-    *ctx_out_len = k;
-    *tail_len = 0;
     return 0;
   }
   const uint8_t* a0 = (const uint8_t*)((uintptr_t)d_in & ~(uintptr_t)15);
   const unsigned long long lo = (unsigned long long)(d_in - a0), hi = lo + n, ng = (hi + 15) / 16;
   const unsigned long long ntiles = (ng + REC_TILE - 1) / REC_TILE;
-  if (ntiles > 0x7FFFFFFFull) return setErr(KX_E_ARG, "kx_split_records_rs: buffer too large");
-  const bool overlap = !rsBorderFree(rs, m);
-  int rc = BatchWs::ensure(W.base.tcount, ntiles * 8);
-  if (!rc) rc = BatchWs::ensure(W.base.toff, ntiles * 8);
-  if (!rc) rc = BatchWs::ensure(W.base.flags, sizeof(Flags));
+  if (ntiles > 0x7FFFFFFFull) return err(KX_E_ARG, "buffer too large");
+  const bool quoted = s.mode == KX_RECORDS_QUOTED, escaped = s.mode == KX_RECORDS_ESCAPED, multi = s.mode == KX_RECORDS_RS;
+  const bool overlap = multi && !rsBorderFree(s.rs, s.rs_len);
+  // the workspace
+  int rc = 0;
+  for (BatchWs::Buf* b : {&W.tcount, &W.toff}) if (!rc) rc = BatchWs::ensure(*b, ntiles * 8);
+  for (BatchWs::Buf* b : {&W.tq, &W.tqoff, &W.tsep, &W.teven}) if (!rc && (quoted || escaped)) rc = BatchWs::ensure(*b, ntiles * 8);
+  if (!rc) rc = BatchWs::ensure(W.flags, (quoted || escaped ? 2 : 1) * sizeof(Flags));
+  if (!rc && escaped) rc = BatchWs::ensure(W.tflag, ntiles * 4);
   if (!rc && overlap) rc = BatchWs::ensure(W.tmap, ntiles * 4);
   if (!rc && overlap) rc = BatchWs::ensure(W.tcnt, ntiles * 32);
-  if (!rc && overlap) rc = BatchWs::ensure(W.info, 4);
+  if (!rc && (escaped || overlap)) rc = BatchWs::ensure(W.info, 4);
   if (rc) return rc;
+  auto U = [](BatchWs::Buf& b) { return (unsigned long long*)b.p; };
+  auto C = [](BatchWs::Buf& b) { return (const unsigned long long*)b.p; };
+  Flags* fl = (Flags*)W.flags.p;
+  uint32_t* tflag = (uint32_t*)W.tflag.p;
+  const dim3 tiles((uint32_t)ntiles), pertile((uint32_t)((ntiles + 255) / 256));
+  // the mode's bytes as the kernels take them (ESCAPED without a quote: no byte is one)
+  const uint32_t spat = 0x01010101u * s.sep, qpat = 0x01010101u * (uint8_t)(s.quote < 0 ? 0 : s.quote), epat = 0x01010101u * (uint8_t)s.escape;
+  const uint32_t qkeep = s.quote < 0 ? 0u : 0xFFFF0000u, x = in.state >> 1, parity_in = in.state & 1u;
+  const uint32_t m = multi ? s.rs_len : 0, k = multi ? in.ctx_len : 0;
   unsigned long long rs8 = 0, ctx8 = 0;
-  for (uint32_t i = 0; i < m; ++i) rs8 |= (unsigned long long)rs[i] << (8 * i);
-  for (uint32_t i = 0; i < k; ++i) ctx8 |= (unsigned long long)ctx[i] << (8 * i);
-  unsigned long long* tcount = (unsigned long long*)W.base.tcount.p;
-  unsigned long long* toff = (unsigned long long*)W.base.toff.p;
-  if (overlap) {
-    hipLaunchKernelGGL(k_rocount, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, rs8, m, ctx8, k, (uint32_t*)W.tmap.p,
-                       (uint32_t*)W.tcnt.p);
-    hipLaunchKernelGGL(k_rsscan, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, m, (uint32_t*)W.tmap.p, (const uint32_t*)W.tcnt.p, tcount,
-                       (uint32_t*)W.info.p);
-  } else {
-    hipLaunchKernelGGL(k_rbcount, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, rs8, m, ctx8, k, tcount);
+  for (uint32_t i = 0; i < m; ++i) rs8 |= (unsigned long long)s.rs[i] << (8 * i);
+  for (uint32_t i = 0; i < k; ++i) ctx8 |= (unsigned long long)in.ctx[i] << (8 * i);
+  // the count step: per tile the selected separators in tcount, then their scan in toff and their total in `flt`
+  switch (s.mode) {
+    case KX_RECORDS_BYTE:
+      hipLaunchKernelGGL(k_rcount, tiles, dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, U(W.tcount));
+      break;
+    case KX_RECORDS_QUOTED:
+      hipLaunchKernelGGL(k_rqcount, tiles, dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, qpat, U(W.tq), U(W.tsep), U(W.teven));
+      hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, C(W.tq), U(W.tqoff), fl);
+      hipLaunchKernelGGL(k_rqselect, pertile, dim3(256), 0, sm, (uint32_t)ntiles, C(W.tqoff), C(W.tsep), C(W.teven), parity_in, U(W.tcount));
+      break;
+    case KX_RECORDS_ESCAPED:
+      hipLaunchKernelGGL(k_recount, tiles, dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, qpat, qkeep, epat, x, U(W.tq), U(W.tsep), U(W.teven), tflag);
+      hipLaunchKernelGGL(k_rescan, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, lo == 0 ? x : 0u, tflag, U(W.tq));
+      hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, C(W.tq), U(W.tqoff), fl);
+      hipLaunchKernelGGL(k_reselect, pertile, dim3(256), 0, sm, (uint32_t)ntiles, (const uint32_t*)tflag, C(W.tq), C(W.tqoff), C(W.tsep),
+                         C(W.teven), parity_in, U(W.tcount), (uint32_t*)W.info.p);
+      break;
+    default:
+      if (overlap) {
+        hipLaunchKernelGGL(k_rocount, tiles, dim3(REC_BT), 0, sm, a0, ng, lo, hi, rs8, m, ctx8, k, (uint32_t*)W.tmap.p, (uint32_t*)W.tcnt.p);
+        hipLaunchKernelGGL(k_rsscan, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, m, (uint32_t*)W.tmap.p, (const uint32_t*)W.tcnt.p, U(W.tcount),
+                           (uint32_t*)W.info.p);
+      } else {
+        hipLaunchKernelGGL(k_rbcount, tiles, dim3(REC_BT), 0, sm, a0, ng, lo, hi, rs8, m, ctx8, k, U(W.tcount));
+      }
   }
-  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, (const unsigned long long*)tcount, toff, (Flags*)W.base.flags.p);
+  Flags* flt = quoted || escaped ? fl + 1 : fl;   // (with quotes the first Flags is the quote scan's)
+  hipLaunchKernelGGL(k_scan_groups, dim3(1), dim3(1024), 0, sm, (uint32_t)ntiles, C(W.tcount), U(W.toff), flt);
   HIPCHECK(hipGetLastError());
-  unsigned long long total = 0;
+  // the total, and what the mode's tail decision reads
+  unsigned long long total = 0, quotes = 0;
   uint32_t info = 0;
-  uint8_t endb[16] = {};   // the context, then the buffer's last nl bytes: every byte that ctx_out or the last candidate can hold
+  uint8_t lastb = 0, endb[16] = {};   // RS: the context, then the buffer's last nl bytes: every byte that out->ctx or the last candidate can hold
   const size_t nl = n < 8 ? n : 8;
-  memcpy(endb, ctx, k);
-  HIPCHECK(hipMemcpyAsync(&total, &((Flags*)W.base.flags.p)->total_len, 8, hipMemcpyDeviceToHost, sm));
-  HIPCHECK(hipMemcpyAsync(endb + k, d_in + n - nl, nl, hipMemcpyDeviceToHost, sm));
-  if (overlap) HIPCHECK(hipMemcpyAsync(&info, W.info.p, 4, hipMemcpyDeviceToHost, sm));
+  const uint8_t* end = endb + k + nl;   // (behind the buffer's last byte)
+  HIPCHECK(hipMemcpyAsync(&total, &flt->total_len, 8, hipMemcpyDeviceToHost, sm));
+  if (quoted) HIPCHECK(hipMemcpyAsync(&quotes, &fl->total_len, 8, hipMemcpyDeviceToHost, sm));
+  if (!escaped && !multi) HIPCHECK(hipMemcpyAsync(&lastb, d_in + n - 1, 1, hipMemcpyDeviceToHost, sm));
+  if (multi) {
+    memcpy(endb, in.ctx, k);
+    HIPCHECK(hipMemcpyAsync(endb + k, d_in + n - nl, nl, hipMemcpyDeviceToHost, sm));
+  }
+  if (escaped || overlap) HIPCHECK(hipMemcpyAsync(&info, W.info.p, 4, hipMemcpyDeviceToHost, sm));
   HIPCHECK(hipStreamSynchronize(sm));
-  const uint8_t* end = endb + k + nl;                                   // (behind the buffer's last byte)
-  const size_t known = n < 8 ? k + n : 8;                               // bytes before `end` that belong to the unfinished record or the buffer
-  // border-free: every copy is selected, so the buffer ends in a separator iff its last m bytes (the context's included) are rs
-  const int tail = overlap ? !(info & 1u) : !(known >= m && !memcmp(end - m, rs, m));
+  // the tail (the buffer's end is no record's end) and the state handed on
+  int tail = 0;
+  switch (s.mode) {
+    case KX_RECORDS_BYTE:
+      tail = lastb != s.sep;
+      break;
+    case KX_RECORDS_QUOTED:
+      out->state = parity_in ^ (uint32_t)(quotes & 1u);
+      tail = !(lastb == s.sep && out->state == 0);   // (a last separator byte inside quotes ends no record)
+      break;
+    case KX_RECORDS_ESCAPED:
+      out->state = (info >> 1) & 3u;
+      tail = !(info & 1u);   // (an escaped separator, or one inside quotes, as the last byte ends no record)
+      break;
+    default: {
+      const size_t known = n < 8 ? k + n : 8;   // bytes before `end` that belong to the unfinished record or the buffer
+      // border-free: every copy is selected, so the buffer ends in a separator iff its last m bytes (the context's included) are rs
+      tail = overlap ? !(info & 1u) : !(known >= m && !memcmp(end - m, s.rs, m));
+    }
+  }
   *nsep = total;
   *nrec = total + (uint64_t)tail;
-  if (cap < *nrec + 1 || !d_off) return setErr(KX_E_CAPACITY, "kx_split_records_rs: offsets buffer too small");
-  if (overlap)
-    hipLaunchKernelGGL(k_rowrite, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, rs8, m, ctx8, k, (const uint32_t*)W.tmap.p,
-                       (const unsigned long long*)toff, (unsigned long long)base, total, tail, (unsigned long long*)d_off);
-  else
-    hipLaunchKernelGGL(k_rbwrite, dim3((uint32_t)ntiles), dim3(REC_BT), 0, sm, a0, ng, lo, hi, rs8, m, ctx8, k, (const unsigned long long*)toff,
-                       (unsigned long long)base, total, tail, (unsigned long long*)d_off);
+  if (cap < *nrec + 1 || !d_off) return err(KX_E_CAPACITY, "offsets buffer too small");
+  // the write step
+  const unsigned long long ubase = base;
+  unsigned long long* uoff = (unsigned long long*)d_off;
+  switch (s.mode) {
+    case KX_RECORDS_BYTE:
+      hipLaunchKernelGGL(k_rwrite, tiles, dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, C(W.toff), ubase, total, tail, uoff);
+      break;
+    case KX_RECORDS_QUOTED:
+      hipLaunchKernelGGL(k_rqwrite, tiles, dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, qpat, C(W.tqoff), parity_in, C(W.toff), ubase, total, tail, uoff);
+      break;
+    case KX_RECORDS_ESCAPED:
+      hipLaunchKernelGGL(k_rewrite, tiles, dim3(REC_BT), 0, sm, a0, ng, lo, hi, spat, qpat, qkeep, epat, x, (const uint32_t*)tflag, C(W.tqoff),
+                         parity_in, C(W.toff), ubase, total, tail, uoff);
+      break;
+    default:
+      if (overlap)
+        hipLaunchKernelGGL(k_rowrite, tiles, dim3(REC_BT), 0, sm, a0, ng, lo, hi, rs8, m, ctx8, k, (const uint32_t*)W.tmap.p, C(W.toff), ubase, total,
+                           tail, uoff);
+      else
+        hipLaunchKernelGGL(k_rbwrite, tiles, dim3(REC_BT), 0, sm, a0, ng, lo, hi, rs8, m, ctx8, k, C(W.toff), ubase, total, tail, uoff);
+  }
   HIPCHECK(hipGetLastError());
-  uint64_t e = base;   // the last selected separator's end
-  if (tail && total) HIPCHECK(hipMemcpyAsync(&e, d_off + total, 8, hipMemcpyDeviceToHost, sm));
+  uint64_t e = base;   // RS: the last selected separator's end
+  if (multi && tail && total) HIPCHECK(hipMemcpyAsync(&e, d_off + total, 8, hipMemcpyDeviceToHost, sm));
   HIPCHECK(hipStreamSynchronize(sm));
-  const uint64_t tl = tail ? n - (e - base) : 0;
-  size_t unfinished = total ? tl : k + n;                               // the unfinished record so far (without a separator: the context's bytes too)
-  if (!tail) unfinished = 0;
-  const size_t co = unfinished < m - 1 ? unfinished : m - 1;            // (≤ 7 ≤ known whenever unfinished ≥ 7)
-  uint8_t tmp[8];
-  memcpy(tmp, end - co, co);
-  memcpy(ctx_out, tmp, co);
-  *ctx_out_len = (uint32_t)co;
-  *tail_len = tl;
+  if (multi) {   // the context handed on, and the tail's length
+    const uint64_t tl = tail ? n - (e - base) : 0;
+    size_t unfinished = total ? tl : k + n;                       // the unfinished record so far (without a separator: the context's bytes too)
+    if (!tail) unfinished = 0;
+    const size_t co = unfinished < m - 1 ? unfinished : m - 1;    // (≤ 7 ≤ known whenever unfinished ≥ 7)
+    memcpy(out->ctx, end - co, co);
+    out->ctx_len = (uint32_t)co;
+    *tail_len = tl;
+  }
   return 0;
 }
 
-// the compute step of kx_run_records_fd, kx_run_records_fd_quoted and kx_run_records_fd_escaped
+// the compute step of the kx_run_records_fd* entry points
 struct RecordsRun {
   kx_program* p = nullptr;
   FdStream* fs = nullptr;
-  uint8_t sep = '\n';
-  int quote = -1;                                      // the quote byte, -1: none (kx_run_records_fd)
-  int escape = -1;                                     // the escape byte, -1: none
-  uint32_t state = 0;                                  // at the start of the next window: bit 0 quote parity, bit 1 escaped
-  uint8_t rs[8] = {}, ctx[8] = {};                     // the multi-byte separator (kx_run_records_fd_rs) and the next window's context
-  uint32_t rs_len = 0, ctx_len = 0;                    // rs_len 0: a one-byte mode
-  bool chomp = false;                                  // records run without their separator
-  uint8_t ors[8] = {};                                 // what follows every accepted record's output
-  uint32_t ors_len = 0;
-  RecQWs qws;
-  RecEWs ews;
-  RecRsWs rws;
+  kx_records_opts o{};                                 // the split, and the framing: chomp, ors (checkRecordsOpts has passed)
+  SplitCarry next;                                     // what the next window's split starts from
   int report_fd = -1;
   RecWs ws;
   BatchWs::Buf off, ooff, docs, carry, one, longest;   // offsets; output offsets; doc records; the straddling record; its offsets
@@ -320,10 +265,10 @@ struct RecordsRun {
   int batch(const uint8_t* in, const uint64_t* d_o, uint64_t ndocs, DevBuf* out, size_t* pos, uint64_t first_rec, bool tail) {
     if (ndocs == 0) return 0;
     kx_batch_frame fr{};
-    fr.trim = chomp ? (rs_len ? rs_len : 1u) : 0u;
+    fr.trim = o.chomp ? (o.mode == KX_RECORDS_RS ? o.rs_len : 1u) : 0u;
     fr.last_whole = tail ? 1u : 0u;
-    fr.suffix_len = ors_len;
-    memcpy(fr.suffix, ors, ors_len);
+    fr.suffix_len = o.ors_len;
+    memcpy(fr.suffix, o.ors, o.ors_len);
     const kx_batch_frame* frp = fr.trim || fr.suffix_len ? &fr : nullptr;
     int rc = BatchWs::ensure(ooff, (ndocs + 1) * 8);
     if (!rc) rc = BatchWs::ensure(docs, ndocs * sizeof(kx_batch_doc));
@@ -367,28 +312,16 @@ struct RecordsRun {
     uint64_t nrec = 0, nsep = 0;
     if (off.cap < 16) { int rc = BatchWs::ensure(off, (n / 32 + 2) * 8); if (rc) return rc; }
     if (timing) HIPCHECK(hipEventRecord(ev[0], nullptr));
-    uint32_t sout = state;
-    uint8_t cout[8] = {};
-    uint32_t cout_len = 0;
+    SplitCarry end;
     uint64_t tail_len = 0;
-    auto split = [&] {
-      if (rs_len)
-        return splitRecordsRs(in, n, rs, rs_len, ctx, ctx_len, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, cout, &cout_len, &tail_len, rws,
-                              nullptr);
-      if (escape >= 0)
-        return splitRecordsEscaped(in, n, sep, quote, (uint8_t)escape, state, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, &sout, ews, nullptr);
-      return quote < 0 ? splitRecords(in, n, sep, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, ws, nullptr)
-                       : splitRecordsQuoted(in, n, sep, (uint8_t)quote, state, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, &sout, qws, nullptr);
-    };
+    auto split = [&] { return splitRecords(o, next, in, n, 0, (uint64_t*)off.p, off.cap / 8, &nrec, &nsep, &end, &tail_len, ws, nullptr); };
     int rc = split();
     if (rc == KX_E_CAPACITY) {
       rc = BatchWs::ensure(off, (nrec + 1) * 8);
       if (!rc) rc = split();
     }
     if (rc) return rc;
-    state = sout;
-    memcpy(ctx, cout, 8);
-    ctx_len = cout_len;
+    next = end;
     if (timing) { HIPCHECK(hipEventRecord(ev[1], nullptr)); HIPCHECK(hipEventSynchronize(ev[1])); st.split_ms += evMs(ev[0], ev[1]); }
     const uint64_t complete = last ? nrec : nsep;   // (a tail that is not the stream's end continues in the next window)
     const uint64_t* d_off = (const uint64_t*)off.p;
@@ -462,55 +395,65 @@ struct RecordsRun {
   }
 };
 
+// what the four kx_split_records* entry points share (n_records is not null): the rules, the pointers, a workspace of its own
+// and the split from *c, which becomes the carry it ends in
+int splitEntry(const char* who, const SplitSpec& s, SplitCarry* c, const void* d_in, size_t n, uint64_t base, uint64_t* d_off, uint64_t cap,
+               uint64_t* n_records, uint64_t* tail_len, void* stream) {
+  *n_records = 0;
+  if (const int rc = checkSplit(s, *c, who)) return rc;
+  if (n && !d_in) return setErr(KX_E_ARG, std::string(who) + ": null input");
+  if (cap && !d_off) return setErr(KX_E_ARG, std::string(who) + ": null offsets with a capacity");
+  RecWs ws;
+  uint64_t nsep = 0;
+  return splitRecords(s, *c, (const uint8_t*)d_in, n, base, d_off, cap, n_records, &nsep, c, tail_len, ws, (hipStream_t)stream);
+}
+
+// the options of a mode's own entry points: no framing
+kx_records_opts plainOpts(uint32_t mode, uint8_t sep, int quote, int escape) {
+  kx_records_opts o{};
+  o.size = sizeof o; o.mode = mode; o.sep = sep; o.quote = quote; o.escape = escape;
+  return o;
+}
+
+// ... with an entry point's (rs, rs_len); a null rs gives rs_len 0, which checkSplit refuses as any other bad length
+kx_records_opts rsOpts(const uint8_t* rs, uint32_t rs_len) {
+  kx_records_opts o = plainOpts(KX_RECORDS_RS, 0, -1, -1);
+  o.rs_len = rs ? rs_len : 0;
+  if (rs && rs_len <= 8) memcpy(o.rs, rs, rs_len);
+  return o;
+}
+
 }  // namespace
 
 extern "C" int kx_split_records(const void* d_in, size_t n, uint8_t sep, uint64_t base, uint64_t* d_off, uint64_t cap, uint64_t* n_records,
                                 void* stream) {
   if (!n_records) return setErr(KX_E_ARG, "null argument");
-  *n_records = 0;
-  if (n && !d_in) return setErr(KX_E_ARG, "kx_split_records: null input");
-  if (cap && !d_off) return setErr(KX_E_ARG, "kx_split_records: null offsets with a capacity");
-  RecWs ws;
-  uint64_t nsep = 0;
-  return splitRecords((const uint8_t*)d_in, n, sep, base, d_off, cap, n_records, &nsep, ws, (hipStream_t)stream);
+  SplitCarry c;
+  uint64_t tl = 0;
+  return splitEntry("kx_split_records", plainOpts(KX_RECORDS_BYTE, sep, -1, -1), &c, d_in, n, base, d_off, cap, n_records, &tl, stream);
 }
 
 extern "C" int kx_split_records_quoted(const void* d_in, size_t n, uint8_t sep, uint8_t quote, uint32_t parity_in, uint64_t base,
                                        uint64_t* d_off, uint64_t cap, uint64_t* n_records, uint32_t* parity_out, void* stream) {
   if (!n_records) return setErr(KX_E_ARG, "null argument");
-  *n_records = 0;
   if (parity_out) *parity_out = 0;
-  if (quote == sep) return setErr(KX_E_ARG, "kx_split_records_quoted: the quote byte cannot be the separator");
-  if (parity_in > 1) return setErr(KX_E_ARG, "kx_split_records_quoted: parity_in must be 0 or 1");
-  if (n && !d_in) return setErr(KX_E_ARG, "kx_split_records_quoted: null input");
-  if (cap && !d_off) return setErr(KX_E_ARG, "kx_split_records_quoted: null offsets with a capacity");
-  RecQWs ws;
-  uint64_t nsep = 0;
-  uint32_t po = parity_in;
-  const int rc = splitRecordsQuoted((const uint8_t*)d_in, n, sep, quote, parity_in, base, d_off, cap, n_records, &nsep, &po, ws,
-                                    (hipStream_t)stream);
-  if (parity_out && (rc == 0 || rc == KX_E_CAPACITY)) *parity_out = po;
+  SplitCarry c;
+  c.state = parity_in;
+  uint64_t tl = 0;
+  const int rc = splitEntry("kx_split_records_quoted", plainOpts(KX_RECORDS_QUOTED, sep, quote, -1), &c, d_in, n, base, d_off, cap, n_records, &tl, stream);
+  if (parity_out && (rc == 0 || rc == KX_E_CAPACITY)) *parity_out = c.state;
   return rc;
 }
 
 extern "C" int kx_split_records_escaped(const void* d_in, size_t n, uint8_t sep, int quote, uint8_t escape, uint32_t state_in, uint64_t base,
                                         uint64_t* d_off, uint64_t cap, uint64_t* n_records, uint32_t* state_out, void* stream) {
   if (!n_records) return setErr(KX_E_ARG, "null argument");
-  *n_records = 0;
   if (state_out) *state_out = 0;
-  if (quote < -1 || quote > 255) return setErr(KX_E_ARG, "kx_split_records_escaped: quote must be a byte value or -1");
-  if (quote == sep) return setErr(KX_E_ARG, "kx_split_records_escaped: the quote byte cannot be the separator");
-  if (escape == sep) return setErr(KX_E_ARG, "kx_split_records_escaped: the escape byte cannot be the separator");
-  if (quote == escape) return setErr(KX_E_ARG, "kx_split_records_escaped: the escape byte cannot be the quote byte");
-  if (state_in > 3 || (quote < 0 && (state_in & 1u))) return setErr(KX_E_ARG, "kx_split_records_escaped: state_in must be 0-3, bit 0 only with a quote");
-  if (n && !d_in) return setErr(KX_E_ARG, "kx_split_records_escaped: null input");
-  if (cap && !d_off) return setErr(KX_E_ARG, "kx_split_records_escaped: null offsets with a capacity");
-  RecEWs ws;
-  uint64_t nsep = 0;
-  uint32_t so = state_in;
-  const int rc = splitRecordsEscaped((const uint8_t*)d_in, n, sep, quote, escape, state_in, base, d_off, cap, n_records, &nsep, &so, ws,
-                                     (hipStream_t)stream);
-  if (state_out && (rc == 0 || rc == KX_E_CAPACITY)) *state_out = so;
+  SplitCarry c;
+  c.state = state_in;
+  uint64_t tl = 0;
+  const int rc = splitEntry("kx_split_records_escaped", plainOpts(KX_RECORDS_ESCAPED, sep, quote, escape), &c, d_in, n, base, d_off, cap, n_records, &tl, stream);
+  if (state_out && (rc == 0 || rc == KX_E_CAPACITY)) *state_out = c.state;
   return rc;
 }
 
@@ -521,20 +464,15 @@ extern "C" int kx_split_records_rs(const void* d_in, size_t n, const uint8_t* rs
   *n_records = 0;
   if (ctx_out_len) *ctx_out_len = 0;
   if (tail_len) *tail_len = 0;
-  if (!rs || rs_len < 1 || rs_len > 8) return setErr(KX_E_ARG, "kx_split_records_rs: the separator must be 1 to 8 bytes");
-  if (ctx_in_len >= rs_len || (ctx_in_len && !ctx_in)) return setErr(KX_E_ARG, "kx_split_records_rs: the context must be shorter than the separator");
-  if (n && !d_in) return setErr(KX_E_ARG, "kx_split_records_rs: null input");
-  if (cap && !d_off) return setErr(KX_E_ARG, "kx_split_records_rs: null offsets with a capacity");
-  RecRsWs ws;
-  uint64_t nsep = 0, tl = 0;
-  uint8_t co[8] = {}, ci[8] = {};
-  uint32_t col = 0;
-  if (ctx_in_len) memcpy(ci, ctx_in, ctx_in_len);
-  const int rc = splitRecordsRs((const uint8_t*)d_in, n, rs, rs_len, ci, ctx_in_len, base, d_off, cap, n_records, &nsep, co, &col, &tl, ws,
-                                (hipStream_t)stream);
+  if (ctx_in_len && !ctx_in) return setErr(KX_E_ARG, "kx_split_records_rs: null context with a length");
+  SplitCarry c;
+  c.ctx_len = ctx_in_len;
+  if (ctx_in_len && ctx_in_len < 8) memcpy(c.ctx, ctx_in, ctx_in_len);   // (8 and more: refused, whatever rs_len is)
+  uint64_t tl = 0;
+  const int rc = splitEntry("kx_split_records_rs", rsOpts(rs, rs_len), &c, d_in, n, base, d_off, cap, n_records, &tl, stream);
   if (rc == 0) {
-    if (ctx_out) memcpy(ctx_out, co, col);
-    if (ctx_out_len) *ctx_out_len = col;
+    if (ctx_out) memcpy(ctx_out, c.ctx, c.ctx_len);
+    if (ctx_out_len) *ctx_out_len = c.ctx_len;
     if (tail_len) *tail_len = tl;
   }
   return rc;
@@ -542,10 +480,19 @@ extern "C" int kx_split_records_rs(const void* d_in, size_t n, const uint8_t* rs
 
 namespace {
 
-// kx_run_records_fd (quote < 0, escape < 0), kx_run_records_fd_quoted (escape < 0), kx_run_records_fd_escaped and, with rs_len > 0,
-// kx_run_records_fd_rs (sep, quote and escape unused)
-int runRecordsFd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, int escape, int report_fd, kx_records_stats* stats,
-                 const uint8_t* rs = nullptr, uint32_t rs_len = 0, bool chomp = false, const uint8_t* ors = nullptr, uint32_t ors_len = 0) {
+// the rules of the five kx_run_records_fd* entry points (`who`)
+int checkRecordsOpts(const kx_records_opts& o, const char* who) {
+  auto no = [&](const char* what) { return setErr(KX_E_ARG, std::string(who) + ": " + what); };
+  if (o.size != sizeof(kx_records_opts)) return no("kx_records_opts::size is not this library's");
+  if (o.pad[0] || o.pad[1] || o.pad[2]) return no("reserved words must be 0");
+  for (uint32_t r : o.reserved) if (r) return no("reserved words must be 0");
+  if (o.ors_len > 8) return no("the output separator is at most 8 bytes");
+  if (o.chomp > 1) return no("chomp must be 0 or 1");
+  return checkSplit(o, SplitCarry{}, who);
+}
+
+// the stream on in_fd in record mode as `o` says (checkRecordsOpts has passed)
+int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o, int report_fd, kx_records_stats* stats) {
   if (!p) return setErr(KX_E_ARG, "null argument");
   if (p->cfg.phase) return setErr(KX_E_ARG, "record mode runs every phase: kx_config::phase must be 0");
   const double t_begin = FdStream::nowMs();
@@ -558,10 +505,7 @@ int runRecordsFd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, i
   fsr.window = (window + fsr.CH - 1) / fsr.CH * fsr.CH;
   (void)hipGetDevice(&fsr.dev);
   RecordsRun R;
-  R.p = p; R.fs = &fsr; R.sep = sep; R.quote = quote; R.escape = escape; R.report_fd = report_fd;
-  if (rs_len) { memcpy(R.rs, rs, rs_len); R.rs_len = rs_len; }
-  R.chomp = chomp;
-  if (ors_len) { memcpy(R.ors, ors, ors_len); R.ors_len = ors_len; }
+  R.p = p; R.fs = &fsr; R.o = o; R.report_fd = report_fd;
   R.timing = p->cfg.collect_timing != 0;
   int rc = 0;
   if (R.timing) for (auto& e : R.ev) if (hipEventCreate(&e) != hipSuccess) rc = setErr(KX_E_HIP, "hipEventCreate failed");
@@ -582,60 +526,33 @@ int runRecordsFd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, i
   return R.rejected ? KX_MATCH_ERROR : 0;
 }
 
+int runRecords(const char* who, kx_program* p, int in_fd, int out_fd, const kx_records_opts& o, int report_fd, kx_records_stats* stats) {
+  if (const int rc = checkRecordsOpts(o, who)) return rc;
+  return runRecordsFd(p, in_fd, out_fd, o, report_fd, stats);
+}
+
 }  // namespace
 
 extern "C" int kx_run_records_fd(kx_program* p, int in_fd, int out_fd, uint8_t sep, int report_fd, kx_records_stats* stats) {
-  return runRecordsFd(p, in_fd, out_fd, sep, -1, -1, report_fd, stats);
+  return runRecords("kx_run_records_fd", p, in_fd, out_fd, plainOpts(KX_RECORDS_BYTE, sep, -1, -1), report_fd, stats);
 }
 
 extern "C" int kx_run_records_fd_quoted(kx_program* p, int in_fd, int out_fd, uint8_t sep, uint8_t quote, int report_fd,
                                         kx_records_stats* stats) {
-  if (quote == sep) return setErr(KX_E_ARG, "kx_run_records_fd_quoted: the quote byte cannot be the separator");
-  return runRecordsFd(p, in_fd, out_fd, sep, quote, -1, report_fd, stats);
+  return runRecords("kx_run_records_fd_quoted", p, in_fd, out_fd, plainOpts(KX_RECORDS_QUOTED, sep, quote, -1), report_fd, stats);
 }
 
 extern "C" int kx_run_records_fd_escaped(kx_program* p, int in_fd, int out_fd, uint8_t sep, int quote, uint8_t escape, int report_fd,
                                          kx_records_stats* stats) {
-  if (quote < -1 || quote > 255) return setErr(KX_E_ARG, "kx_run_records_fd_escaped: quote must be a byte value or -1");
-  if (quote == sep) return setErr(KX_E_ARG, "kx_run_records_fd_escaped: the quote byte cannot be the separator");
-  if (escape == sep) return setErr(KX_E_ARG, "kx_run_records_fd_escaped: the escape byte cannot be the separator");
-  if (quote == escape) return setErr(KX_E_ARG, "kx_run_records_fd_escaped: the escape byte cannot be the quote byte");
-  return runRecordsFd(p, in_fd, out_fd, sep, quote, escape, report_fd, stats);
+  return runRecords("kx_run_records_fd_escaped", p, in_fd, out_fd, plainOpts(KX_RECORDS_ESCAPED, sep, quote, escape), report_fd, stats);
 }
 
 extern "C" int kx_run_records_fd_rs(kx_program* p, int in_fd, int out_fd, const uint8_t* rs, uint32_t rs_len, int report_fd,
                                     kx_records_stats* stats) {
-  if (!rs || rs_len < 1 || rs_len > 8) return setErr(KX_E_ARG, "kx_run_records_fd_rs: the separator must be 1 to 8 bytes");
-  return runRecordsFd(p, in_fd, out_fd, 0, -1, -1, report_fd, stats, rs, rs_len);
+  return runRecords("kx_run_records_fd_rs", p, in_fd, out_fd, rsOpts(rs, rs_len), report_fd, stats);
 }
 
 extern "C" int kx_run_records_fd_opts(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, int report_fd, kx_records_stats* stats) {
   if (!o) return setErr(KX_E_ARG, "null argument");
-  if (o->size != sizeof(kx_records_opts)) return setErr(KX_E_ARG, "kx_run_records_fd_opts: kx_records_opts::size is not this library's");
-  if (o->pad[0] || o->pad[1] || o->pad[2]) return setErr(KX_E_ARG, "kx_run_records_fd_opts: reserved words must be 0");
-  for (uint32_t r : o->reserved) if (r) return setErr(KX_E_ARG, "kx_run_records_fd_opts: reserved words must be 0");
-  if (o->ors_len > 8) return setErr(KX_E_ARG, "kx_run_records_fd_opts: the output separator is at most 8 bytes");
-  if (o->chomp > 1) return setErr(KX_E_ARG, "kx_run_records_fd_opts: chomp must be 0 or 1");
-  const bool chomp = o->chomp != 0;
-  const int sep = o->sep, quote = o->quote, escape = o->escape;
-  switch (o->mode) {
-    case KX_RECORDS_BYTE:
-      return runRecordsFd(p, in_fd, out_fd, o->sep, -1, -1, report_fd, stats, nullptr, 0, chomp, o->ors, o->ors_len);
-    case KX_RECORDS_QUOTED:
-      if (quote < 0 || quote > 255) return setErr(KX_E_ARG, "kx_run_records_fd_opts: quote must be a byte value");
-      if (quote == sep) return setErr(KX_E_ARG, "kx_run_records_fd_opts: the quote byte cannot be the separator");
-      return runRecordsFd(p, in_fd, out_fd, o->sep, quote, -1, report_fd, stats, nullptr, 0, chomp, o->ors, o->ors_len);
-    case KX_RECORDS_ESCAPED:
-      if (quote < -1 || quote > 255) return setErr(KX_E_ARG, "kx_run_records_fd_opts: quote must be a byte value or -1");
-      if (escape < 0 || escape > 255) return setErr(KX_E_ARG, "kx_run_records_fd_opts: escape must be a byte value");
-      if (quote == sep) return setErr(KX_E_ARG, "kx_run_records_fd_opts: the quote byte cannot be the separator");
-      if (escape == sep) return setErr(KX_E_ARG, "kx_run_records_fd_opts: the escape byte cannot be the separator");
-      if (quote == escape) return setErr(KX_E_ARG, "kx_run_records_fd_opts: the escape byte cannot be the quote byte");
-      return runRecordsFd(p, in_fd, out_fd, o->sep, quote, escape, report_fd, stats, nullptr, 0, chomp, o->ors, o->ors_len);
-    case KX_RECORDS_RS:
-      if (o->rs_len < 1 || o->rs_len > 8) return setErr(KX_E_ARG, "kx_run_records_fd_opts: the separator must be 1 to 8 bytes");
-      return runRecordsFd(p, in_fd, out_fd, 0, -1, -1, report_fd, stats, o->rs, o->rs_len, chomp, o->ors, o->ors_len);
-    default:
-      return setErr(KX_E_ARG, "kx_run_records_fd_opts: no such split mode");
-  }
+  return runRecords("kx_run_records_fd_opts", p, in_fd, out_fd, *o, report_fd, stats);
 }

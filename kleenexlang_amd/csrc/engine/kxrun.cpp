@@ -132,6 +132,13 @@ static bool parseOutputSeparator(const char* a, uint8_t* ors, uint32_t* len) {
   return parseSeparatorString(a, ors, len);
 }
 
+// the engine's `name`; without it, null after the message that this library has none and which option (`needs`) wants a newer one
+static void* engineSymbol(void* h, const char* argv0, const char* name, const char* needs) {
+  void* f = dlsym(h, name);
+  if (!f) fprintf(stderr, "%s: this libkxhip.so has no %s (%s a newer engine library)\n", argv0, name, needs);
+  return f;
+}
+
 int main(int argc, char** argv) {
   // locate the payload appended to this executable
   FILE* self = fopen("/proc/self/exe", "rb");
@@ -228,23 +235,17 @@ int main(int argc, char** argv) {
   int rc;
   kx_config cfg = configFromEnv();
   if (records) {
-    auto runr = (int (*)(kx_program*, int, int, uint8_t, int, kx_records_stats*))dlsym(h, "kx_run_records_fd");
-    if (!runr) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd (--records needs a newer engine library)\n", argv[0]); return 1; }
-    auto runq = (int (*)(kx_program*, int, int, uint8_t, uint8_t, int, kx_records_stats*))dlsym(h, "kx_run_records_fd_quoted");
-    if (quoted && !runq) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_quoted (--quote needs a newer engine library)\n", argv[0]); return 1; }
-    auto rune = (int (*)(kx_program*, int, int, uint8_t, int, uint8_t, int, kx_records_stats*))dlsym(h, "kx_run_records_fd_escaped");
-    if (escaped && !rune) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_escaped (--escape needs a newer engine library)\n", argv[0]); return 1; }
-    int (*runm)(kx_program*, int, int, const uint8_t*, uint32_t, int, kx_records_stats*) = nullptr;
-    if (multi) {
-      runm = (decltype(runm))dlsym(h, "kx_run_records_fd_rs");
-      if (!runm) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_rs (--rs needs a newer engine library)\n", argv[0]); return 1; }
-    }
     const bool framing = chomp || ors_len;   // (--ors= alone is the default: no output separator)
-    int (*runo)(kx_program*, int, int, const kx_records_opts*, int, kx_records_stats*) = nullptr;
-    if (framing) {
-      runo = (decltype(runo))dlsym(h, "kx_run_records_fd_opts");
-      if (!runo) { fprintf(stderr, "%s: this libkxhip.so has no kx_run_records_fd_opts (--chomp and --ors need a newer engine library)\n", argv[0]); return 1; }
-    }
+    auto runr = (decltype(&kx_run_records_fd))engineSymbol(h, argv[0], "kx_run_records_fd", "--records needs");
+    decltype(&kx_run_records_fd_quoted) runq = nullptr;
+    decltype(&kx_run_records_fd_escaped) rune = nullptr;
+    decltype(&kx_run_records_fd_rs) runm = nullptr;
+    decltype(&kx_run_records_fd_opts) runo = nullptr;
+    if (!runr) return 1;
+    if (quoted && !(runq = (decltype(runq))engineSymbol(h, argv[0], "kx_run_records_fd_quoted", "--quote needs"))) return 1;
+    if (escaped && !(rune = (decltype(rune))engineSymbol(h, argv[0], "kx_run_records_fd_escaped", "--escape needs"))) return 1;
+    if (multi && !(runm = (decltype(runm))engineSymbol(h, argv[0], "kx_run_records_fd_rs", "--rs needs"))) return 1;
+    if (framing && !(runo = (decltype(runo))engineSymbol(h, argv[0], "kx_run_records_fd_opts", "--chomp and --ors need"))) return 1;
     // record mode is where the single-document route is unusable (a third of a millisecond per record): stages with register
     // actions are replayed by the batch kernels unless KX_BATCH_ACTIONS=0 asks for the route
     if (!cfg.batch_actions) cfg.batch_actions = 2;

@@ -427,48 +427,48 @@ def _check_values(values, what):
         raise ValueError("%s: values must be contiguous" % what)
 
 
-def split_records_tensor(values, sep=b"\n"):
-    """kx_split_records: the record offsets of a CUDA uint8 tensor (any start address) as an int64 device tensor of
-    n_records + 1 entries, relative to values[0] — the offsets run_batch_tensor takes.  Runs on the current stream, blocks."""
-    _check_values(values, "split_records_tensor")
-    s = _check_sep(sep)
+def _records_mode(quote, escape, rs):
+    """KX_RECORDS_* of the keywords of a record-mode call (`rs` comes alone; an `escape` may come with a `quote`)."""
+    return KX_RECORDS_RS if rs is not None else KX_RECORDS_ESCAPED if escape is not None else \
+        KX_RECORDS_QUOTED if quote is not None else KX_RECORDS_BYTE
+
+
+def _split_tensor(what, values, entry, checks, outs=()):
+    """What the split_*_tensor functions (`what`) share: the checks of `values`, then `checks()` — the function's own, giving
+    the C arguments of `entry` between n and base — the size query, the allocation and the split.  `outs`: the C arguments
+    behind n_records.  Returns the offsets."""
+    _check_values(values, what)
+    args = checks()
     import torch
     if not values.is_cuda:
-        raise EngineError("split_records_tensor: values must be on a HIP device (there is no CPU fallback)")
+        raise EngineError("%s: values must be on a HIP device (there is no CPU fallback)" % what)
     lib = load_engine()
+    call = getattr(lib, entry)
     stream = ctypes.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)
     vptr = ctypes.c_void_p(values.data_ptr() if values.numel() else None)
     n = ctypes.c_uint64()
-    rc = lib.kx_split_records(vptr, values.numel(), s, 0, None, 0, ctypes.byref(n), stream)
+    rc = call(vptr, values.numel(), *args, 0, None, 0, ctypes.byref(n), *outs, stream)
     if rc not in (0, -3):
         raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
     off = torch.empty(n.value + 1, dtype=torch.int64, device=values.device)
-    rc = lib.kx_split_records(vptr, values.numel(), s, 0, ctypes.c_void_p(off.data_ptr()), off.numel(), ctypes.byref(n), stream)
+    rc = call(vptr, values.numel(), *args, 0, ctypes.c_void_p(off.data_ptr()), off.numel(), ctypes.byref(n), *outs, stream)
     if rc:
         raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
     return off
 
 
+def split_records_tensor(values, sep=b"\n"):
+    """kx_split_records: the record offsets of a CUDA uint8 tensor (any start address) as an int64 device tensor of
+    n_records + 1 entries, relative to values[0] — the offsets run_batch_tensor takes.  Runs on the current stream, blocks."""
+    return _split_tensor("split_records_tensor", values, "kx_split_records", lambda: (_check_sep(sep),))
+
+
 def split_quoted_records_tensor(values, sep=b"\n", quote=b'"', parity=0):
     """kx_split_records_quoted: split_records_tensor where a separator inside quotes ends no record (split_records_model's
     `quote`).  `parity` is the quote parity at values[0].  Returns (offsets, parity after the last byte)."""
-    _check_values(values, "split_quoted_records_tensor")
-    s, q, par = _check_sep(sep), _check_quote(quote, sep), _check_parity(parity)
-    import torch
-    if not values.is_cuda:
-        raise EngineError("split_quoted_records_tensor: values must be on a HIP device (there is no CPU fallback)")
-    lib = load_engine()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)
-    vptr = ctypes.c_void_p(values.data_ptr() if values.numel() else None)
-    n, pout = ctypes.c_uint64(), ctypes.c_uint32()
-    rc = lib.kx_split_records_quoted(vptr, values.numel(), s, q, par, 0, None, 0, ctypes.byref(n), ctypes.byref(pout), stream)
-    if rc not in (0, -3):
-        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
-    off = torch.empty(n.value + 1, dtype=torch.int64, device=values.device)
-    rc = lib.kx_split_records_quoted(vptr, values.numel(), s, q, par, 0, ctypes.c_void_p(off.data_ptr()), off.numel(), ctypes.byref(n),
-                                     ctypes.byref(pout), stream)
-    if rc:
-        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
+    pout = ctypes.c_uint32()
+    off = _split_tensor("split_quoted_records_tensor", values, "kx_split_records_quoted",
+                        lambda: (_check_sep(sep), _check_quote(quote, sep), _check_parity(parity)), (ctypes.byref(pout),))
     return off, pout.value
 
 
@@ -476,51 +476,23 @@ def split_escaped_records_tensor(values, sep=b"\n", quote=None, escape=b"\\", st
     """kx_split_records_escaped: split_records_tensor where an escaped byte is only data and, with a `quote` byte, a separator
     inside quotes ends no record (split_escaped_records_model).  `state` is the state at values[0] (bit 0 quote parity, bit 1
     escaped).  Returns (offsets, state after the last byte)."""
-    _check_values(values, "split_escaped_records_tensor")
-    s = _check_sep(sep)
-    q = -1 if quote is None else _check_quote(quote, sep)
-    e = _check_escape(escape, sep, quote)
-    st = _check_state(state, quote)
-    import torch
-    if not values.is_cuda:
-        raise EngineError("split_escaped_records_tensor: values must be on a HIP device (there is no CPU fallback)")
-    lib = load_engine()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)
-    vptr = ctypes.c_void_p(values.data_ptr() if values.numel() else None)
-    n, sout = ctypes.c_uint64(), ctypes.c_uint32()
-    rc = lib.kx_split_records_escaped(vptr, values.numel(), s, q, e, st, 0, None, 0, ctypes.byref(n), ctypes.byref(sout), stream)
-    if rc not in (0, -3):
-        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
-    off = torch.empty(n.value + 1, dtype=torch.int64, device=values.device)
-    rc = lib.kx_split_records_escaped(vptr, values.numel(), s, q, e, st, 0, ctypes.c_void_p(off.data_ptr()), off.numel(), ctypes.byref(n),
-                                      ctypes.byref(sout), stream)
-    if rc:
-        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
+    sout = ctypes.c_uint32()
+    off = _split_tensor("split_escaped_records_tensor", values, "kx_split_records_escaped",
+                        lambda: (_check_sep(sep), -1 if quote is None else _check_quote(quote, sep), _check_escape(escape, sep, quote),
+                                 _check_state(state, quote)), (ctypes.byref(sout),))
     return off, sout.value
 
 
 def split_rs_records_tensor(values, rs, ctx=b""):
     """kx_split_records_rs: split_records_tensor for a separator `rs` of 1 to 8 bytes (split_rs_records_model); `ctx` is the
     context before values[0].  Returns (offsets, (ctx_out, tail_len))."""
-    _check_values(values, "split_rs_records_tensor")
-    rs = _check_rs(rs)
-    ctx = _check_ctx(ctx, rs)
-    import torch
-    if not values.is_cuda:
-        raise EngineError("split_rs_records_tensor: values must be on a HIP device (there is no CPU fallback)")
-    lib = load_engine()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(values.device).cuda_stream)
-    vptr = ctypes.c_void_p(values.data_ptr() if values.numel() else None)
-    n, col, tl = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint64()
-    cout = (ctypes.c_uint8 * 8)()
-    rc = lib.kx_split_records_rs(vptr, values.numel(), rs, len(rs), ctx, len(ctx), 0, None, 0, ctypes.byref(n), None, None, None, stream)
-    if rc not in (0, -3):
-        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
-    off = torch.empty(n.value + 1, dtype=torch.int64, device=values.device)
-    rc = lib.kx_split_records_rs(vptr, values.numel(), rs, len(rs), ctx, len(ctx), 0, ctypes.c_void_p(off.data_ptr()), off.numel(),
-                                 ctypes.byref(n), cout, ctypes.byref(col), ctypes.byref(tl), stream)
-    if rc:
-        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
+    def checks():
+        r = _check_rs(rs)
+        c = _check_ctx(ctx, r)
+        return r, len(r), c, len(c)
+
+    col, tl, cout = ctypes.c_uint32(), ctypes.c_uint64(), (ctypes.c_uint8 * 8)()
+    off = _split_tensor("split_rs_records_tensor", values, "kx_split_records_rs", checks, (cout, ctypes.byref(col), ctypes.byref(tl)))
     return off, (bytes(cout[:col.value]), tl.value)
 
 
@@ -1181,14 +1153,15 @@ class Program:
         data = bytes(data)
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         v = torch.frombuffer(bytearray(data), dtype=torch.uint8).to(dev) if data else torch.empty(0, dtype=torch.uint8, device=dev)
-        if rs is not None:
+        mode = _records_mode(quote, escape, rs)
+        if mode == KX_RECORDS_RS:
             offs, (_, tail_len) = split_rs_records_tensor(v, rs)
             tail = tail_len > 0                          # (the splitter's own report)
         else:
-            if escape is not None:
+            if mode == KX_RECORDS_ESCAPED:
                 offs, _ = split_escaped_records_tensor(v, sep, quote, escape)
                 model = lambda d: split_escaped_records_model(d, sep, quote, escape)[0]   # noqa: E731
-            elif quote is not None:
+            elif mode == KX_RECORDS_QUOTED:
                 offs, _ = split_quoted_records_tensor(v, sep, quote)
                 model = lambda d: split_records_model(d, sep, quote)                      # noqa: E731
             else:
@@ -1225,26 +1198,19 @@ class Program:
         q = None if quote is None else _check_quote(quote, sep)
         e = None if escape is None else _check_escape(escape, sep, quote)
         chomp, ors = _check_chomp(chomp), _check_ors(ors)
+        mode, qi = _records_mode(q, e, rs), -1 if q is None else q
         st = KxRecordsStats()
         with self._batch_actions_for_call(batch_actions):
-            if chomp or ors:
-                o = KxRecordsOpts(size=ctypes.sizeof(KxRecordsOpts), sep=s, quote=-1 if q is None else q, escape=-1 if e is None else e,
-                                  chomp=1 if chomp else 0, ors_len=len(ors))
-                o.mode = KX_RECORDS_RS if rs is not None else KX_RECORDS_ESCAPED if e is not None else \
-                    KX_RECORDS_QUOTED if q is not None else KX_RECORDS_BYTE
-                if rs is not None:
-                    o.rs[:len(rs)] = rs
-                    o.rs_len = len(rs)
+            if chomp or ors:                             # the framing: only kx_run_records_fd_opts has it
+                o = KxRecordsOpts(size=ctypes.sizeof(KxRecordsOpts), mode=mode, sep=s, quote=qi, escape=-1 if e is None else e,
+                                  rs_len=len(rs or b""), chomp=1 if chomp else 0, ors_len=len(ors))
+                o.rs[:o.rs_len] = rs or b""
                 o.ors[:len(ors)] = ors
-                rc = self._lib.kx_run_records_fd_opts(self._h, in_fd, out_fd, ctypes.byref(o), report_fd, ctypes.byref(st))
-            elif rs is not None:
-                rc = self._lib.kx_run_records_fd_rs(self._h, in_fd, out_fd, rs, len(rs), report_fd, ctypes.byref(st))
-            elif e is not None:
-                rc = self._lib.kx_run_records_fd_escaped(self._h, in_fd, out_fd, s, -1 if q is None else q, e, report_fd, ctypes.byref(st))
-            elif q is None:
-                rc = self._lib.kx_run_records_fd(self._h, in_fd, out_fd, s, report_fd, ctypes.byref(st))
-            else:
-                rc = self._lib.kx_run_records_fd_quoted(self._h, in_fd, out_fd, s, q, report_fd, ctypes.byref(st))
+                name, args = "kx_run_records_fd_opts", (ctypes.byref(o),)
+            else:                                        # the mode's own entry point
+                name, args = (("kx_run_records_fd", (s,)), ("kx_run_records_fd_quoted", (s, q)), ("kx_run_records_fd_escaped", (s, qi, e)),
+                              ("kx_run_records_fd_rs", (rs, len(rs or b""))))[mode]
+            rc = getattr(self._lib, name)(self._h, in_fd, out_fd, *args, report_fd, ctypes.byref(st))
         self.last_records_stats = st
         if rc not in (0, 1):
             raise EngineError(self._err())

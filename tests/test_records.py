@@ -119,3 +119,70 @@ def test_python_argument_errors_before_any_device():
         prog.run_records_fd(0, 1, report_fd=None)
     with pytest.raises(ValueError):
         prog.run_records_fd(0, 1, sep=300)
+
+
+def test_abi_refusals_of_every_mode_before_any_device():
+    """The argument rules of the four kx_split_records* and the four kx_run_records_fd* entry points of the modes: every bad
+    argument is KX_E_ARG (-4) with null device pointers and a null program, so before anything touches a device.  That the rule
+    made the refusal, not the null: the same call with good arguments is KX_E_CAPACITY (-3, the size query of an empty buffer)
+    for a split, and for a run it leaves another message (the null program's)."""
+    lib = ctypes.CDLL(os.path.join(build.OUT, "libkxhip.so"))
+    lib.kx_last_error.restype = ctypes.c_char_p
+    vp, u8, u32, u64, ci = ctypes.c_void_p, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
+    n, w = ctypes.c_uint64(), ctypes.c_uint32()
+    nref, wref = ctypes.byref(n), ctypes.byref(w)
+    lib.kx_split_records.argtypes = [vp, ctypes.c_size_t, u8, u64, vp, u64, vp, vp]
+    lib.kx_split_records_quoted.argtypes = [vp, ctypes.c_size_t, u8, u8, u32, u64, vp, u64, vp, vp, vp]
+    lib.kx_split_records_escaped.argtypes = [vp, ctypes.c_size_t, u8, ci, u8, u32, u64, vp, u64, vp, vp, vp]
+    lib.kx_split_records_rs.argtypes = [vp, ctypes.c_size_t, ctypes.c_char_p, u32, ctypes.c_char_p, u32, u64, vp, u64, vp, vp, vp, vp, vp]
+    split = {   # (d_in, n) = (null, 0) in front of `mid`; base, d_off, cap, n_records behind it; then the mode's outputs and the stream
+        "byte": lambda mid, nr=nref, cap=0, size=0: lib.kx_split_records(None, size, *mid, 0, None, cap, nr, None),
+        "quoted": lambda mid, nr=nref: lib.kx_split_records_quoted(None, 0, *mid, 0, None, 0, nr, wref, None),
+        "escaped": lambda mid, nr=nref: lib.kx_split_records_escaped(None, 0, *mid, 0, None, 0, nr, wref, None),
+        "rs": lambda mid, nr=nref: lib.kx_split_records_rs(None, 0, *mid, 0, None, 0, nr, None, None, None, None),
+    }
+    good = {"byte": (10,), "quoted": (10, 34, 0), "escaped": (10, 34, 92, 0), "rs": (b"\r\n", 2, b"\r", 1)}
+    bad = {"byte": [],
+           "quoted": [(10, 10, 0),                                  # quote == sep
+                      (10, 34, 2)],                                 # parity_in 2
+           "escaped": [(10, 10, 92, 0),                             # quote == sep
+                       (10, -1, 10, 0), (10, 34, 10, 0),            # escape == sep
+                       (10, 34, 34, 0),                             # quote == escape
+                       (10, 256, 92, 0), (10, -2, 92, 0),           # quote no byte value, nor -1
+                       (10, 34, 92, 4),                             # state_in 4
+                       (10, -1, 92, 1), (10, -1, 92, 3)],           # bit 0 of state_in without a quote
+           "rs": [(b"", 0, b"", 0), (b"123456789", 9, b"", 0),      # rs_len 0 and 9
+                  (None, 2, b"", 0),
+                  (b"\r\n", 2, b"\r\n", 2), (b"\r\n", 2, b"\r\n\r", 3), (b"\r\n", 2, None, 1)]}   # ctx_in_len == rs_len, and more
+    for mode, f in split.items():
+        assert f(good[mode]) == -3, mode
+        assert f(good[mode], nr=None) == -4, mode                   # a null n_records
+        for mid in bad[mode]:
+            assert f(mid) == -4, (mode, mid)
+    assert split["byte"]((10,), cap=1) == -4 and split["byte"]((10,), size=1) == -4   # a capacity without offsets, a size without input
+    # the edges of the rules from inside: still accepted
+    for mid in ((10, 34, 1), (10, 255, 0)):
+        assert split["quoted"](mid) == -3, mid
+    for mid in ((10, 34, 92, 3), (10, -1, 92, 2), (10, 255, 0, 0)):
+        assert split["escaped"](mid) == -3, mid
+    for mid in ((b"x", 1, b"", 0), (b"12345678", 8, b"1234567", 7)):
+        assert split["rs"](mid) == -3, mid
+
+    head, tail = [vp, ci, ci], [ci, vp]
+    lib.kx_run_records_fd.argtypes = head + [u8] + tail
+    lib.kx_run_records_fd_quoted.argtypes = head + [u8, u8] + tail
+    lib.kx_run_records_fd_escaped.argtypes = head + [u8, ci, u8] + tail
+    lib.kx_run_records_fd_rs.argtypes = head + [ctypes.c_char_p, u32] + tail
+    run = {"byte": lib.kx_run_records_fd, "quoted": lib.kx_run_records_fd_quoted, "escaped": lib.kx_run_records_fd_escaped,
+           "rs": lib.kx_run_records_fd_rs}
+    good = {"byte": (10,), "quoted": (10, 34), "escaped": (10, 34, 92), "rs": (b"\r\n", 2)}
+    bad = {"byte": [],
+           "quoted": [(10, 10)],
+           "escaped": [(10, 10, 92), (10, -1, 10), (10, 34, 10), (10, 34, 34), (10, 256, 92), (10, -2, 92)],
+           "rs": [(b"", 0), (b"123456789", 9), (None, 2)]}
+    for mode, g in run.items():
+        assert g(None, 0, 1, *good[mode], -1, None) == -4, mode     # the null program
+        null_program = lib.kx_last_error()
+        for mid in bad[mode]:
+            assert g(None, 0, 1, *mid, -1, None) == -4, (mode, mid)
+            assert lib.kx_last_error() != null_program, (mode, mid)

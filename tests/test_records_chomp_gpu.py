@@ -428,3 +428,64 @@ def test_copy_through_reproduces_the_input(tmp_path_factory, spelling, sep):
         assert (res.returncode, res.stderr) == (0, b"") and res.stdout == data      # ends in a separator: byte for byte
         res = _run_bin(exe, split + ["--chomp", "--ors=" + spelling], data + b"the tail", window)
         assert (res.returncode, res.stderr) == (0, b"") and res.stdout == data + b"the tail" + sep   # a tail: the input plus one separator
+
+
+# ---------------------------------------------------------------------------------------------------------- 10. no framing
+# takes every byte the records below hold but a digit, the separators included: without --chomp they reach the program
+WHOLE = 'main := ("[" /[a-z,"]+/ "]" | /\\\\/ | ~/\\n/ "\\\\n" | ~/\\r/ "\\\\r")*\n'
+# per mode: the keywords of MODES as the C arguments of the mode's own entry point and as kx_records_opts fields; the pieces of a
+# record (each leaves the quote parity even and no escape open); (piece, k): a piece to lay with its byte k on a window border —
+# a record, open quotes, an open escape, half a separator then cross it; and a tail
+PLAIN = {
+    "byte": ("kx_run_records_fd", (10,), dict(mode=host.KX_RECORDS_BYTE, sep=10, quote=-1, escape=-1),
+             [b"ab", b",", b"c"], [(b"ab", 1)], b"ab,c"),
+    "quoted": ("kx_run_records_fd_quoted", (10, 34), dict(mode=host.KX_RECORDS_QUOTED, sep=10, quote=34, escape=-1),
+               [b"ab", b'"a\nb"', b'"\n"', b"c"], [(b'"a\nb"', 2)], b'ab"c\n'),
+    "escaped": ("kx_run_records_fd_escaped", (10, 34, 92), dict(mode=host.KX_RECORDS_ESCAPED, sep=10, quote=34, escape=92),
+                [b"ab", b'"a\nb"', b"\\\\", b"\\\n", b"c"], [(b"\\\n", 1), (b'"a\nb"', 2)], b'ab"c\\"\n'),
+    "rs": ("kx_run_records_fd_rs", (b"\r\n", 2), dict(mode=host.KX_RECORDS_RS, rs_len=2, quote=-1, escape=-1),
+           [b"ab", b",", b"\n", b"\r", b"c"], [(b"ab\r\n", 3)], b"ab\r"),
+}
+
+
+@pytest.mark.parametrize("mode", sorted(PLAIN))
+def test_opts_without_framing_is_the_modes_own_entry_point(mode, tmp_path, monkeypatch):
+    """include/kxhip.h: with chomp = 0 and ors_len = 0, kx_run_records_fd_opts is the entry point of its mode — the same output,
+    report, return code and counts, over 4 KiB windows with a record, the quote parity, an escape and half a separator crossing
+    their borders, rejected records in between and a tail."""
+    W = 4096
+    monkeypatch.setenv("KX_WINDOW_BYTES", str(W))
+    name, own_args, fields, pieces, straddlers, tail = PLAIN[mode]
+    sep = b"\r\n" if mode == "rs" else b"\n"
+    r = random.Random(len(mode))
+    data, border = bytearray(), W
+    for i in range(1500):
+        if len(data) >= border - 100:                                               # (a record is at most 78 bytes)
+            piece, k = straddlers[(border // W - 1) % len(straddlers)]
+            data += b"c" * (border - len(data) - k) + piece
+            assert data[border - k:border - k + len(piece)] == piece
+            data += b"" if piece.endswith(sep) else b"ab" + sep
+            border += W
+        data += b"".join(r.choice(pieces) for _ in range(r.randrange(0, 16))) + (b"1" if i % 9 == 4 else b"") + sep
+    data = bytes(data) + tail
+    assert border > 3 * W
+    (tmp_path / "in.dat").write_bytes(data)
+    prog = Program(blob_of(WHOLE))
+
+    def call(name, args):
+        st = host.KxRecordsStats()
+        with open(tmp_path / "in.dat", "rb") as fi, open(tmp_path / "out.dat", "wb") as fo, open(tmp_path / "err.dat", "wb") as fe:
+            rc = getattr(prog._lib, name)(prog._h, fi.fileno(), fo.fileno(), *args, fe.fileno(), ctypes.byref(st))
+        counts = {k: getattr(st, k) for k in ("records", "records_rejected", "windows", "in_bytes", "out_bytes", "longest_record")}
+        return rc, (tmp_path / "out.dat").read_bytes(), (tmp_path / "err.dat").read_bytes(), counts
+
+    own = call(name, own_args)
+    o = host.KxRecordsOpts(size=ctypes.sizeof(host.KxRecordsOpts), chomp=0, ors_len=0, **fields)
+    o.rs[:2] = b"\r\n"                                                              # (read in KX_RECORDS_RS only)
+    opts = call("kx_run_records_fd_opts", (ctypes.byref(o),))
+    for what, a, b in zip(("return code", "output", "report", "counts"), own, opts):
+        assert a == b, (mode, what, a[:200] if isinstance(a, bytes) else a, b[:200] if isinstance(b, bytes) else b)
+    rc, out, err, counts = own
+    model = MODES[mode][1] if mode != "byte" else (lambda d: host.split_records_model(d, b"\n"))
+    assert rc == 1 and counts["records"] == len(model(data)) - 1 and counts["in_bytes"] == len(data) and counts["windows"] > 3
+    assert 90 <= counts["records_rejected"] == err.count(b"\n") < counts["records"] // 2 and len(out) == counts["out_bytes"] > len(data) // 2
