@@ -349,6 +349,63 @@ typedef struct kx_records_opts {
 } kx_records_opts;
 int kx_run_records_fd_opts(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, int report_fd, kx_records_stats* stats);
 
+/* ---- field mode: the program runs on one field of every record, the rest of the record is copied ---------------------------------
+ * kx_run_batch_fields is kx_run_batch where document i is FIELD `field` (counted from 1) of the record d_in[d_in_off[i], d_in_off[i+1]).
+ * The record's BODY is its range without its last sep_len bytes (the record separator; with last_whole != 0 record n_docs - 1 has
+ * none and is body to its end).  The body's fields lie between its live `fs` bytes: every one (quote = escape = -1); one at even
+ * parity of the `quote` bytes before it IN THE RECORD (quote >= 0, escape = -1); one that is unescaped and at even parity of the
+ * record's unescaped quotes (escape >= 0, quote a byte or -1) — the rules of the quoted and the escaped record split, from state 0
+ * at the record's first byte.  A body with f live separators has f + 1 fields; the empty body has one empty field; nothing is
+ * stripped from a field.  The program runs on the field as a whole input (every stage; its result is kx_run_device's for those
+ * bytes alone), and
+ *   accepted record i: its output d_out[d_out_off[i], d_out_off[i+1]) is body[0, field begin) + the program's output +
+ *     body[field end, body end) + the record's own separator (keep_sep != 0, and the record has one) + suffix[0, suffix_len);
+ *     d_docs[i] = {0, 0, 0}
+ *   record i rejected by the program: its output range is empty; d_docs[i] = {fail_pos, 1, fail_stage}, fail_pos counted in the field
+ *   record i with fewer than `field` fields: its output range is empty; d_docs[i] = {fields found, 2, 0}; the program is not run on
+ *     it.  It counts as rejected (the return code, stats->docs_rejected).
+ * Return codes, KX_E_CAPACITY with *out_len = the spliced bytes needed (d_out_off and d_docs are filled; d_out = NULL, cap = 0 is
+ * the size query), the routed and replayed documents and everything else are kx_run_batch's.  KX_E_ARG besides: decreasing offsets
+ * or a range shorter than sep_len other than a whole last one (found on the device before any kernel reads a record); a wrong
+ * `size`, field = 0, fs equal to quote or escape, quote = escape, sep_len or suffix_len > 8, a non-zero reserved word (found before
+ * any device work).  Per call the library holds 48 bytes of workspace per record, the fields' bytes and the program's output. */
+typedef struct kx_batch_fields {
+  uint32_t size;         /* sizeof(kx_batch_fields) */
+  uint32_t field;        /* K: 1 to 2^32 - 1 */
+  uint8_t fs;            /* the field separator */
+  uint8_t pad[3];        /* must be 0 */
+  int32_t quote;         /* a byte value, or -1: none */
+  int32_t escape;        /* a byte value, or -1: none */
+  uint32_t sep_len;      /* 0 to 8: the last sep_len bytes of every range are the record's separator */
+  uint32_t last_whole;   /* != 0: the last record has no separator */
+  uint32_t keep_sep;     /* != 0: a record's separator follows its output */
+  uint32_t suffix_len;   /* 0 to 8 */
+  uint8_t suffix[8];
+  uint32_t reserved[4];  /* must be 0 */
+} kx_batch_fields;
+int kx_run_batch_fields(kx_program* prog, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_fields* fields,
+                        void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs, size_t* out_len, kx_batch_stats* stats,
+                        void* stream);
+/* HIP-event times of field mode's own kernels (locate; gather; the two scans, the second with the kernel that measures the
+   records' outputs; splice), summed over the program's kx_run_batch_fields calls so far; with kx_config::collect_timing, else 0. */
+typedef struct kx_fields_kernel_stats {
+  float locate_ms, gather_ms, scan_ms, splice_ms;
+  uint64_t calls;
+} kx_fields_kernel_stats;
+int kx_fields_stats(const kx_program* prog, kx_fields_kernel_stats* out);
+
+/* kx_run_records_fd_opts in field mode (`BIN --records … --field=K --fs=F`): every record the split of `o` delivers goes through
+ * kx_run_batch_fields with field K = `field` (1 to 2^32 - 1) and the field separator `fs` — the quote and the escape byte of the
+ * split decide which fs bytes are live, the separator (1 byte, or rs_len) is never part of the body, whether or not o->chomp is
+ * set, the stream's tail has none.  An accepted record writes body[0, field) + the program's output + body[field end, end), then its
+ * own separator unless o->chomp (a tail has none), then o->ors.  A record the program rejects writes nothing and reports
+ * "Match error at input symbol S in record R!" with S counted inside the field; a record with fewer than K fields writes nothing,
+ * reports "Record R has no field K!" and counts in records_rejected.  KX_E_ARG besides kx_run_records_fd_opts's: field = 0, fs equal
+ * to the one-byte record separator (sep, or rs with rs_len = 1), to the quote or to the escape byte of the mode (a byte of a multi-byte
+ * rs may equal fs). */
+int kx_run_records_fd_fields(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, uint32_t field, uint8_t fs, int report_fd,
+                             kx_records_stats* stats);
+
 /* ---- sharded execution: one contiguous shard of the input per GPU -------------
  * Per stage and per rank:
  *   kx_shard_begin → kx_shard_forward → [exchange kx_fwd_summary] → kx_shard_fix_head

@@ -20,6 +20,10 @@
 // separator.  Only the stream's tail keeps its whole range: the last window's batch has last_whole = 1 when the split reported a
 // tail, and the carried record is left whole when it is that tail (the last window brought no separator).  The splitters know
 // nothing of this.
+//
+// Field mode (kx_run_records_fd_fields): RecordsRun::batch calls kx_run_batch_fields (kx_fields_host.inc) instead — the carried
+// record and the window's records alike — with the split's quote and escape byte, the separator's length and, unless `chomp`, the
+// separator kept behind the record's output.  A record without the field is reported in a line of its own kind.
 
 namespace {
 
@@ -230,6 +234,8 @@ struct RecordsRun {
   kx_program* p = nullptr;
   FdStream* fs = nullptr;
   kx_records_opts o{};                                 // the split, and the framing: chomp, ors (checkRecordsOpts has passed)
+  uint32_t field = 0;                                  // field mode: the program runs on field `field` (0: on the record)
+  uint8_t fsep = 0;                                    //   ... of the fields that `fsep` separates
   SplitCarry next;                                     // what the next window's split starts from
   int report_fd = -1;
   RecWs ws;
@@ -250,7 +256,8 @@ struct RecordsRun {
     if (report_fd < 0) return 0;
     std::string s;
     for (uint64_t i = 0; i < n; ++i)
-      if (d[i].status) s += "Match error at input symbol " + std::to_string(d[i].fail_pos) + " in record " + std::to_string(first_rec + i) + "!\n";
+      if (d[i].status == 2) s += "Record " + std::to_string(first_rec + i) + " has no field " + std::to_string(field) + "!\n";
+      else if (d[i].status) s += "Match error at input symbol " + std::to_string(d[i].fail_pos) + " in record " + std::to_string(first_rec + i) + "!\n";
     for (size_t w = 0; w < s.size();) {
       const ssize_t r = write(report_fd, s.data() + w, s.size() - w);
       if (r < 0) { if (errno == EINTR) continue; return setErr(KX_E_IO, "write of the record report failed"); }
@@ -270,13 +277,26 @@ struct RecordsRun {
     fr.suffix_len = o.ors_len;
     memcpy(fr.suffix, o.ors, o.ors_len);
     const kx_batch_frame* frp = fr.trim || fr.suffix_len ? &fr : nullptr;
+    kx_batch_fields fl{};
+    fl.size = sizeof fl; fl.field = field; fl.fs = fsep;
+    fl.quote = o.mode == KX_RECORDS_QUOTED || o.mode == KX_RECORDS_ESCAPED ? o.quote : -1;
+    fl.escape = o.mode == KX_RECORDS_ESCAPED ? o.escape : -1;
+    fl.sep_len = o.mode == KX_RECORDS_RS ? o.rs_len : 1u;
+    fl.last_whole = tail ? 1u : 0u;
+    fl.keep_sep = o.chomp ? 0u : 1u;
+    fl.suffix_len = o.ors_len;
+    memcpy(fl.suffix, o.ors, o.ors_len);
+    auto run = [&](void* d_out, size_t cap, size_t* ol, kx_batch_stats* bs) {
+      return field ? kx_run_batch_fields(p, in, d_o, ndocs, &fl, d_out, cap, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, ol, bs, nullptr)
+                   : kx_run_batch_framed(p, in, d_o, ndocs, frp, d_out, cap, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, ol, bs, nullptr);
+    };
     int rc = BatchWs::ensure(ooff, (ndocs + 1) * 8);
     if (!rc) rc = BatchWs::ensure(docs, ndocs * sizeof(kx_batch_doc));
     if (rc) return rc;
     kx_batch_stats bs{};
     size_t ol = 0;
     if (timing) HIPCHECK(hipEventRecord(ev[2], nullptr));
-    rc = kx_run_batch_framed(p, in, d_o, ndocs, frp, out->d + *pos, out->cap - *pos, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, &ol, &bs, nullptr);
+    rc = run(out->d + *pos, out->cap - *pos, &ol, &bs);
     if (rc == KX_E_CAPACITY) {
       DevBuf nb;
       rc = fs->pool.get(*pos + ol + ol / 8 + 4096, &nb);
@@ -284,7 +304,7 @@ struct RecordsRun {
       if (*pos) HIPCHECK(hipMemcpy(nb.d, out->d, *pos, hipMemcpyDeviceToDevice));
       fs->pool.put(*out);
       *out = nb;
-      rc = kx_run_batch_framed(p, in, d_o, ndocs, frp, out->d + *pos, out->cap - *pos, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, &ol, &bs, nullptr);
+      rc = run(out->d + *pos, out->cap - *pos, &ol, &bs);
     }
     if (timing) { HIPCHECK(hipEventRecord(ev[3], nullptr)); HIPCHECK(hipEventSynchronize(ev[3])); st.batch_ms += evMs(ev[2], ev[3]); }
     if (rc != 0 && rc != KX_MATCH_ERROR) return rc;
@@ -480,19 +500,26 @@ extern "C" int kx_split_records_rs(const void* d_in, size_t n, const uint8_t* rs
 
 namespace {
 
-// the rules of the five kx_run_records_fd* entry points (`who`)
-int checkRecordsOpts(const kx_records_opts& o, const char* who) {
+// the rules of the six kx_run_records_fd* entry points (`who`); fs: the field separator of field mode, or -1
+int checkRecordsOpts(const kx_records_opts& o, const char* who, int fs = -1) {
   auto no = [&](const char* what) { return setErr(KX_E_ARG, std::string(who) + ": " + what); };
   if (o.size != sizeof(kx_records_opts)) return no("kx_records_opts::size is not this library's");
   if (o.pad[0] || o.pad[1] || o.pad[2]) return no("reserved words must be 0");
   for (uint32_t r : o.reserved) if (r) return no("reserved words must be 0");
   if (o.ors_len > 8) return no("the output separator is at most 8 bytes");
   if (o.chomp > 1) return no("chomp must be 0 or 1");
-  return checkSplit(o, SplitCarry{}, who);
+  if (const int rc = checkSplit(o, SplitCarry{}, who)) return rc;
+  if (fs < 0) return 0;
+  if (o.mode != KX_RECORDS_RS && fs == (int)o.sep) return no("the field separator cannot be the record separator");
+  if (o.mode == KX_RECORDS_RS && o.rs_len == 1 && fs == (int)o.rs[0]) return no("the field separator cannot be the record separator");
+  if ((o.mode == KX_RECORDS_QUOTED || o.mode == KX_RECORDS_ESCAPED) && fs == o.quote) return no("the field separator cannot be the quote byte");
+  if (o.mode == KX_RECORDS_ESCAPED && fs == o.escape) return no("the field separator cannot be the escape byte");
+  return 0;
 }
 
 // the stream on in_fd in record mode as `o` says (checkRecordsOpts has passed)
-int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o, int report_fd, kx_records_stats* stats) {
+int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o, int report_fd, kx_records_stats* stats, uint32_t field = 0,
+                 uint8_t fsep = 0) {
   if (!p) return setErr(KX_E_ARG, "null argument");
   if (p->cfg.phase) return setErr(KX_E_ARG, "record mode runs every phase: kx_config::phase must be 0");
   const double t_begin = FdStream::nowMs();
@@ -505,7 +532,7 @@ int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o,
   fsr.window = (window + fsr.CH - 1) / fsr.CH * fsr.CH;
   (void)hipGetDevice(&fsr.dev);
   RecordsRun R;
-  R.p = p; R.fs = &fsr; R.o = o; R.report_fd = report_fd;
+  R.p = p; R.fs = &fsr; R.o = o; R.report_fd = report_fd; R.field = field; R.fsep = fsep;
   R.timing = p->cfg.collect_timing != 0;
   int rc = 0;
   if (R.timing) for (auto& e : R.ev) if (hipEventCreate(&e) != hipSuccess) rc = setErr(KX_E_HIP, "hipEventCreate failed");
@@ -555,4 +582,12 @@ extern "C" int kx_run_records_fd_rs(kx_program* p, int in_fd, int out_fd, const 
 extern "C" int kx_run_records_fd_opts(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, int report_fd, kx_records_stats* stats) {
   if (!o) return setErr(KX_E_ARG, "null argument");
   return runRecords("kx_run_records_fd_opts", p, in_fd, out_fd, *o, report_fd, stats);
+}
+
+extern "C" int kx_run_records_fd_fields(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, uint32_t field, uint8_t fs, int report_fd,
+                                        kx_records_stats* stats) {
+  if (!o) return setErr(KX_E_ARG, "null argument");
+  if (field == 0) return setErr(KX_E_ARG, "kx_run_records_fd_fields: field numbers start at 1");
+  if (const int rc = checkRecordsOpts(*o, "kx_run_records_fd_fields", fs)) return rc;
+  return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, field, fs);
 }

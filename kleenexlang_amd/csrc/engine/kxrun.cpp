@@ -16,7 +16,10 @@
 // (kx_run_records_fd_escaped, with or without --quote).  With `--rs=STR` the separator is the 1 to 8 bytes STR spells, and records
 // end after its leftmost, non-overlapping copies (kx_run_records_fd_rs).  With `--chomp` every record is run without its separator
 // (a last record without one is run whole), and with `--ors=STR` the 0 to 8 bytes STR spells follow the output of every accepted
-// record (kx_run_records_fd_opts): the framing is the command line's, the program sees only the record.
+// record (kx_run_records_fd_opts): the framing is the command line's, the program sees only the record.  With `--field=K` the
+// program runs on field K of every record — the fields lie between the `--fs=F` bytes (default a tab) that the quote and the
+// escape rules leave live — and the rest of the record is copied around its output (kx_run_records_fd_fields); a record with
+// fewer fields writes nothing and is reported as "Record R has no field K!".  What --field and --fs refuse exits with status 2.
 //
 // BIN = this executable ++ KXP blob ++ libdir ++ trailer (see kexc main.cpp).
 // The engine is loaded with dlopen so that this file carries no HIP dependency.
@@ -79,6 +82,7 @@ static void usage(const char* name) {
   fprintf(stdout, "- \"%s --records --rs=STR\": records end after the 1 to 8 bytes STR spells (\\r\\n, \\n\\n, \\xHH ...), leftmost and non-overlapping.\n", name);
   fprintf(stdout, "- \"%s --records ... --chomp\": every record is run without its separator (a last record without one is run whole).\n", name);
   fprintf(stdout, "- \"%s --records ... --ors=STR\": the 0 to 8 bytes STR spells follow the output of every accepted record.\n", name);
+  fprintf(stdout, "- \"%s --records ... --field=K [--fs=F]\": runs field K (from 1; fields end at F, default a tab) of every record, the rest is copied.\n", name);
 }
 
 // --records=SEP, --quote=Q, --escape=E: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
@@ -162,10 +166,13 @@ int main(int argc, char** argv) {
   static struct option long_options[] = {{"phase", required_argument, 0, 'p'}, {"gpus", required_argument, 0, 'g'},
                                          {"records", optional_argument, 0, 'r'}, {"quote", optional_argument, 0, 'q'},
                                          {"escape", optional_argument, 0, 'e'}, {"rs", required_argument, 0, 's'},
-                                         {"chomp", no_argument, 0, 'c'}, {"ors", required_argument, 0, 'o'}, {0, 0, 0, 0}};
+                                         {"chomp", no_argument, 0, 'c'}, {"ors", required_argument, 0, 'o'},
+                                         {"field", required_argument, 0, 'f'}, {"fs", required_argument, 0, 'F'}, {0, 0, 0, 0}};
   bool timing = false, records = false, quoted = false, escaped = false, sep_given = false, multi = false, chomp = false, ors_given = false;
   uint8_t sep = '\n', quote = '"', escape = '\\', rs[8] = {}, ors[8] = {};
-  uint32_t rs_len = 0, ors_len = 0;
+  uint32_t rs_len = 0, ors_len = 0, field = 0;
+  bool field_given = false, fs_given = false;
+  uint8_t fsep = '\t';
   long phase = 0, gpus = 0;
   int c;
   while ((c = getopt_long(argc, argv, "ihtp:", long_options, nullptr)) != -1) {
@@ -203,6 +210,18 @@ int main(int argc, char** argv) {
         ors_given = true;
         if (!parseOutputSeparator(optarg, ors, &ors_len)) { fprintf(stderr, "Invalid output record separator: %s\n", optarg); return 1; }
         break;
+      case 'f': {
+        field_given = true;
+        char* end = nullptr;
+        const unsigned long long v = (*optarg >= '0' && *optarg <= '9') ? strtoull(optarg, &end, 10) : 0;
+        if (!end || *end || v < 1 || v > 0xFFFFFFFFull || strlen(optarg) > 10) { fprintf(stderr, "Invalid --field: %s (a number from 1 to 4294967295)\n", optarg); return 2; }
+        field = (uint32_t)v;
+        break;
+      }
+      case 'F':
+        fs_given = true;
+        if (!parseSeparator(optarg, &fsep)) { fprintf(stderr, "Invalid --fs: %s (one byte)\n", optarg); return 2; }
+        break;
       case 'h':
       default: usage(argv[0]); return 1;
     }
@@ -220,6 +239,11 @@ int main(int argc, char** argv) {
   if (multi && (quoted || escaped)) { fprintf(stderr, "%s: --rs cannot be combined with --quote or --escape\n", argv[0]); return 1; }
   if (chomp && !records) { fprintf(stderr, "%s: --chomp needs --records\n", argv[0]); return 1; }
   if (ors_given && !records) { fprintf(stderr, "%s: --ors needs --records\n", argv[0]); return 1; }
+  if (field_given && !records) { fprintf(stderr, "%s: --field needs --records\n", argv[0]); return 2; }
+  if (fs_given && !field_given) { fprintf(stderr, "%s: --fs needs --field\n", argv[0]); return 2; }
+  if (field_given && (multi ? rs_len == 1 && fsep == rs[0] : fsep == sep)) { fprintf(stderr, "%s: --fs cannot be the record separator\n", argv[0]); return 2; }
+  if (field_given && quoted && fsep == quote) { fprintf(stderr, "%s: --fs cannot be the --quote character\n", argv[0]); return 2; }
+  if (field_given && escaped && fsep == escape) { fprintf(stderr, "%s: --fs cannot be the --escape character\n", argv[0]); return 2; }
   struct timeval t0, t1;
   if (timing) gettimeofday(&t0, nullptr);
 
@@ -241,10 +265,12 @@ int main(int argc, char** argv) {
     decltype(&kx_run_records_fd_escaped) rune = nullptr;
     decltype(&kx_run_records_fd_rs) runm = nullptr;
     decltype(&kx_run_records_fd_opts) runo = nullptr;
+    decltype(&kx_run_records_fd_fields) runf = nullptr;
     if (!runr) return 1;
     if (quoted && !(runq = (decltype(runq))engineSymbol(h, argv[0], "kx_run_records_fd_quoted", "--quote needs"))) return 1;
     if (escaped && !(rune = (decltype(rune))engineSymbol(h, argv[0], "kx_run_records_fd_escaped", "--escape needs"))) return 1;
     if (multi && !(runm = (decltype(runm))engineSymbol(h, argv[0], "kx_run_records_fd_rs", "--rs needs"))) return 1;
+    if (field_given && !(runf = (decltype(runf))engineSymbol(h, argv[0], "kx_run_records_fd_fields", "--field needs"))) return 1;
     if (framing && !(runo = (decltype(runo))engineSymbol(h, argv[0], "kx_run_records_fd_opts", "--chomp and --ors need"))) return 1;
     // record mode is where the single-document route is unusable (a third of a millisecond per record): stages with register
     // actions are replayed by the batch kernels unless KX_BATCH_ACTIONS=0 asks for the route
@@ -252,7 +278,7 @@ int main(int argc, char** argv) {
     kx_program* prog = nullptr;
     if (load(blob.data(), blob.size(), &cfg, &prog)) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 1; }
     kx_records_stats rs_stats;
-    if (framing) {
+    if (framing || field_given) {
       kx_records_opts o{};
       o.size = sizeof o;
       o.mode = multi ? KX_RECORDS_RS : escaped ? KX_RECORDS_ESCAPED : quoted ? KX_RECORDS_QUOTED : KX_RECORDS_BYTE;
@@ -262,7 +288,8 @@ int main(int argc, char** argv) {
       memcpy(o.rs, rs, 8); o.rs_len = rs_len;
       o.chomp = chomp ? 1u : 0u;
       memcpy(o.ors, ors, 8); o.ors_len = ors_len;
-      rc = runo(prog, STDIN_FILENO, STDOUT_FILENO, &o, STDERR_FILENO, &rs_stats);
+      rc = field_given ? runf(prog, STDIN_FILENO, STDOUT_FILENO, &o, field, fsep, STDERR_FILENO, &rs_stats)
+                       : runo(prog, STDIN_FILENO, STDOUT_FILENO, &o, STDERR_FILENO, &rs_stats);
     } else if (multi) rc = runm(prog, STDIN_FILENO, STDOUT_FILENO, rs, rs_len, STDERR_FILENO, &rs_stats);
     else if (escaped) rc = rune(prog, STDIN_FILENO, STDOUT_FILENO, sep, quoted ? (int)quote : -1, escape, STDERR_FILENO, &rs_stats);
     else rc = quoted ? runq(prog, STDIN_FILENO, STDOUT_FILENO, sep, quote, STDERR_FILENO, &rs_stats) : runr(prog, STDIN_FILENO, STDOUT_FILENO, sep, STDERR_FILENO, &rs_stats);

@@ -41,6 +41,14 @@ class MatchError(KleenexError):
         self.stage = stage
 
 
+class NoFieldError(KleenexError):
+    """Field mode: the record has fewer fields than the one asked for.  `fields` = the fields it has."""
+
+    def __init__(self, fields):
+        super().__init__("the record has only %d field(s)" % fields)
+        self.fields = fields
+
+
 class KxStats(ctypes.Structure):
     _fields_ = [("fail_pos", ctypes.c_uint64), ("fail_stage", ctypes.c_uint32),
                 ("unsynced_segments", ctypes.c_uint32), ("in_bytes", ctypes.c_uint64),
@@ -417,6 +425,98 @@ class KxRecordsOpts(ctypes.Structure):
                 ("chomp", ctypes.c_uint32), ("ors", ctypes.c_uint8 * 8), ("ors_len", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
 
 
+class KxBatchFields(ctypes.Structure):
+    """include/kxhip.h::kx_batch_fields."""
+    _fields_ = [("size", ctypes.c_uint32), ("field", ctypes.c_uint32), ("fs", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3),
+                ("quote", ctypes.c_int32), ("escape", ctypes.c_int32), ("sep_len", ctypes.c_uint32), ("last_whole", ctypes.c_uint32),
+                ("keep_sep", ctypes.c_uint32), ("suffix_len", ctypes.c_uint32), ("suffix", ctypes.c_uint8 * 8),
+                ("reserved", ctypes.c_uint32 * 4)]
+
+
+class KxFieldsKernelStats(ctypes.Structure):
+    """include/kxhip.h::kx_fields_kernel_stats."""
+    _fields_ = [(k, ctypes.c_float) for k in ("locate_ms", "gather_ms", "scan_ms", "splice_ms")] + [("calls", ctypes.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+def _check_field(field):
+    """A field number: an int in [1, 2^32) → the int."""
+    if isinstance(field, bool) or not isinstance(field, int):
+        raise TypeError("field: an int from 1, not %s" % type(field).__name__)
+    if not 1 <= field < 1 << 32:
+        raise ValueError("field: %d is not in [1, 2^32)" % field)
+    return field
+
+
+def _check_fs(fs, quote=None, escape=None, sep=None):
+    """A field separator: one byte, not the quote, the escape or the (one-byte) record separator `sep` → the int."""
+    f = _one_byte(fs, "field separator")
+    if sep is not None and f == _one_byte(sep, "record separator"):
+        raise ValueError("field separator: %r is also the record separator" % bytes([f]))
+    if quote is not None and f == _one_byte(quote, "quote character"):
+        raise ValueError("field separator: %r is also the quote character" % bytes([f]))
+    if escape is not None and f == _one_byte(escape, "escape character"):
+        raise ValueError("field separator: %r is also the escape character" % bytes([f]))
+    return f
+
+
+def _check_sep_len(sep_len):
+    if isinstance(sep_len, bool) or not isinstance(sep_len, int):
+        raise TypeError("sep_len: an int from 0 to 8, not %s" % type(sep_len).__name__)
+    if not 0 <= sep_len <= 8:
+        raise ValueError("sep_len: %d is not in [0, 8]" % sep_len)
+    return sep_len
+
+
+def field_records_model(data, offsets, sep_len, last_whole, field, fs, quote=None, escape=None):
+    """kx_run_batch_fields's view of its records in pure Python — the normative model of `--field`: record i of `data` is
+    data[offsets[i]:offsets[i+1]]; its body is that range without its last `sep_len` bytes (the separator), the last record whole
+    with `last_whole`.  The body's fields lie between its live `fs` bytes: every one; with a `quote` byte one at even parity of
+    the quote bytes before it in the record; with an `escape` byte one that is unescaped and at even parity of the record's
+    unescaped quotes (an escaped byte is only data).  A body with f live separators has f + 1 fields, the empty body one empty
+    field.  Returns, per record, (prefix, field, rest, separator) — body = prefix + field + rest, field number `field` from 1 — or
+    the number of fields the record has if that is fewer.  Raises ValueError for a range shorter than `sep_len`."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError("field_records_model: data must be bytes, not %s" % type(data).__name__)
+    sep_len, field = _check_sep_len(sep_len), _check_field(field)
+    if not isinstance(last_whole, bool):
+        raise TypeError("field_records_model: last_whole must be True or False, not %s" % type(last_whole).__name__)
+    f = _check_fs(fs, quote, escape)
+    q = None if quote is None else _one_byte(quote, "quote character")
+    e = None if escape is None else _one_byte(escape, "escape character")
+    if q is not None and q == e:
+        raise ValueError("escape character: %r is also the quote character" % bytes([e]))
+    data, offs = bytes(data), [int(o) for o in offsets]
+    check_batch_offsets(offs, len(data))
+    n, res = len(offs) - 1, []
+    for i in range(n):
+        t = 0 if last_whole and i == n - 1 else sep_len
+        if offs[i + 1] - offs[i] < t:
+            raise ValueError("field_records_model: record %d is shorter than its separator (%d)" % (i, t))
+        body, sep = data[offs[i]:offs[i + 1] - t], data[offs[i + 1] - t:offs[i + 1]]
+        cuts, parity, esc = [], 0, False                      # the positions of the live separators
+        for k, b in enumerate(body):
+            if esc:
+                esc = False
+            elif e is not None and b == e:
+                esc = True
+            elif q is not None and b == q:
+                parity ^= 1
+            elif b == f and parity == 0:
+                cuts.append(k)
+                if len(cuts) == field:
+                    break
+        if len(cuts) < field - 1:
+            res.append(len(cuts) + 1)
+            continue
+        lo = cuts[field - 2] + 1 if field > 1 else 0
+        hi = cuts[field - 1] if len(cuts) >= field else len(body)
+        res.append((body[:lo], body[lo:hi], body[hi:], sep))
+    return res
+
+
 def _check_values(values, what):
     import torch
     if not isinstance(values, torch.Tensor):
@@ -583,6 +683,11 @@ def load_engine():
         lib.kx_run_batch.argtypes = [vp, vp, vp, u64, vp, sz, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(KxBatchStats), vp]
         lib.kx_run_batch_framed.argtypes = [vp, vp, vp, u64, ctypes.POINTER(KxBatchFrame), vp, sz, vp, vp, ctypes.POINTER(sz),
                                             ctypes.POINTER(KxBatchStats), vp]
+        lib.kx_run_batch_fields.argtypes = [vp, vp, vp, u64, ctypes.POINTER(KxBatchFields), vp, sz, vp, vp, ctypes.POINTER(sz),
+                                            ctypes.POINTER(KxBatchStats), vp]
+        lib.kx_fields_stats.argtypes = [vp, ctypes.POINTER(KxFieldsKernelStats)]
+        lib.kx_run_records_fd_fields.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), u32, ctypes.c_uint8,
+                                                 ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
         lib.kx_run_records_fd_opts.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.c_int,
                                                ctypes.POINTER(KxRecordsStats)]
         lib.kx_split_records.argtypes = [vp, sz, ctypes.c_uint8, u64, vp, u64, ctypes.POINTER(u64), vp]
@@ -1032,9 +1137,14 @@ class Program:
         if trim or last_whole or suffix:
             frame = KxBatchFrame(trim=trim, last_whole=1 if last_whole else 0, suffix_len=len(suffix))
             frame.suffix[:len(suffix)] = bytes(suffix)
+        return self._run_batch_call("run_batch_tensor", values, offsets, out, frame, None)
+
+    def _run_batch_call(self, what, values, offsets, out, frame, fields):
+        """The device part of run_batch_tensor (`frame`: a KxBatchFrame or None) and run_batch_fields_tensor (`fields`: a
+        KxBatchFields): the checks that need the tensors' device, the buffers, the size query and the call."""
         import torch
         if not values.is_cuda:
-            raise EngineError("run_batch_tensor: values must be on a HIP device (there is no CPU fallback)")
+            raise EngineError("%s: values must be on a HIP device (there is no CPU fallback)" % what)
         dev = values.device
         if not offsets.is_cuda:
             offsets = offsets.to(dev)
@@ -1054,7 +1164,12 @@ class Program:
             st = KxBatchStats()
             bptr = ctypes.c_void_p(buf.data_ptr() if buf is not None and buf.numel() else None)
             bcap = buf.numel() if buf is not None else 0
-            if frame is None:
+            if fields is not None:
+                rc = self._lib.kx_run_batch_fields(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
+                                                   ctypes.byref(fields), bptr, bcap, ctypes.c_void_p(out_off.data_ptr()),
+                                                   ctypes.c_void_p(docs.data_ptr()), ctypes.byref(ol), ctypes.byref(st),
+                                                   ctypes.c_void_p(stream))
+            elif frame is None:
                 rc = self._lib.kx_run_batch(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n, bptr, bcap,
                                             ctypes.c_void_p(out_off.data_ptr()), ctypes.c_void_p(docs.data_ptr()), ctypes.byref(ol),
                                             ctypes.byref(st), ctypes.c_void_p(stream))
@@ -1075,7 +1190,7 @@ class Program:
                 out = torch.empty(0, dtype=torch.uint8, device=dev)
         else:
             if not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous()):
-                raise TypeError("run_batch_tensor: out must be a contiguous CUDA uint8 tensor")
+                raise TypeError("%s: out must be a contiguous CUDA uint8 tensor" % what)
             rc, need = call(out)
         if rc == -3:
             raise EngineError("output buffer too small: need %d bytes" % need)
@@ -1083,6 +1198,39 @@ class Program:
             raise EngineError(self._err())
         d = docs[:n]
         return out[:need], out_off, (d[:, 1] & 0xFFFFFFFF).to(torch.int32), d[:, 0], (d[:, 1] >> 32).to(torch.int32)
+
+    def run_batch_fields_tensor(self, values, offsets, field, fs=b"\t", quote=None, escape=None, sep_len=0, last_whole=False,
+                                keep_sep=True, suffix=b"", out=None):
+        """Field mode (kx_run_batch_fields): run_batch_tensor where the program runs on field `field` (from 1) of record i =
+        values[offsets[i]:offsets[i+1]] and the rest of the record is copied around its output (field_records_model): an accepted
+        record's output is prefix + program output + rest, then its separator (its last `sep_len` bytes; the last record has none
+        with `last_whole`) if `keep_sep`, then the 0 to 8 `suffix` bytes.  Returns the five tensors of run_batch_tensor; status 2 =
+        the record has fewer fields, fail_pos[i] of them."""
+        _check_batch_args(values, offsets)
+        field, sep_len = _check_field(field), _check_sep_len(sep_len)
+        f = _check_fs(fs, quote, escape)
+        q = -1 if quote is None else _one_byte(quote, "quote character")
+        e = -1 if escape is None else _one_byte(escape, "escape character")
+        if q >= 0 and q == e:
+            raise ValueError("escape character: %r is also the quote character" % bytes([e]))
+        for name, v in (("last_whole", last_whole), ("keep_sep", keep_sep)):
+            if not isinstance(v, bool):
+                raise TypeError("run_batch_fields_tensor: %s must be True or False, not %s" % (name, type(v).__name__))
+        if not isinstance(suffix, (bytes, bytearray)):
+            raise TypeError("run_batch_fields_tensor: suffix must be bytes of length 0 to 8, not %s" % type(suffix).__name__)
+        if len(suffix) > 8:
+            raise ValueError("run_batch_fields_tensor: suffix must be 0 to 8 bytes, not %d" % len(suffix))
+        spec = KxBatchFields(size=ctypes.sizeof(KxBatchFields), field=field, fs=f, quote=q, escape=e, sep_len=sep_len,
+                             last_whole=1 if last_whole else 0, keep_sep=1 if keep_sep else 0, suffix_len=len(suffix))
+        spec.suffix[:len(suffix)] = bytes(suffix)
+        return self._run_batch_call("run_batch_fields_tensor", values, offsets, out, None, spec)
+
+    def fields_kernel_stats(self):
+        """kx_fields_stats: HIP-event times of field mode's own kernels, summed over this program's calls (collect_timing)."""
+        st = KxFieldsKernelStats()
+        if self._lib.kx_fields_stats(self._h, ctypes.byref(st)):
+            raise EngineError(self._err())
+        return st.as_dict()
 
     def run_batch(self, docs, device=None):
         """Convenience form of run_batch_tensor: a list of bytes → a list holding, per document, its output bytes or a
@@ -1129,7 +1277,8 @@ class Program:
             raise ValueError("%s: rs= cannot be combined with quote= or escape=" % what)
         return rs
 
-    def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None, batch_actions=True, rs=None, chomp=False, ors=b""):
+    def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None, batch_actions=True, rs=None, chomp=False, ors=b"",
+                    field=None, fs=b"\t"):
         """Record mode on bytes: every record of `data` (split after each `sep` byte, kx_split_records on the device) is a
         whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage).  With a `quote` byte
         a separator inside quotes ends no record (kx_split_records_quoted from parity 0).  With an `escape` byte an escaped
@@ -1138,10 +1287,16 @@ class Program:
         bytes; not with a `sep`, `quote` or `escape`) records end after the leftmost, non-overlapping copies of rs
         (kx_split_records_rs from an empty context).  With `chomp` every record is run without its separator (a tail, which
         has no valid one, whole) and the 0 to 8 bytes `ors` end the output of every accepted record (kx_run_batch_framed,
-        chomp_records_model)."""
+        chomp_records_model).  With `field` (from 1) the program runs on that field of every record — the fields lie between the
+        live `fs` bytes — and the rest of the record is copied around its output (kx_run_batch_fields, field_records_model): the
+        separator is never part of the body, and follows the output unless `chomp`; a record with fewer fields gives a
+        NoFieldError."""
         if not isinstance(data, (bytes, bytearray, memoryview)):
             raise TypeError("run_records: data must be bytes, not %s" % type(data).__name__)
         chomp, ors = _check_chomp(chomp), _check_ors(ors)
+        if field is not None:
+            field = _check_field(field)
+            _check_fs(fs, quote, escape, sep if rs is None else rs if len(rs) == 1 else None)
         if rs is not None:
             rs = self._check_rs_alone(rs, sep, quote, escape, "run_records")
         _check_sep(sep)
@@ -1170,25 +1325,32 @@ class Program:
             # tail: the last record has no valid separator.  The record starts at a boundary, where the split's state is 0, so
             # the split model says it: with one more byte behind the record, its end is a boundary iff a separator ends it.
             # (`data` is bytes here, whatever came in; reading offs[-2] waits for the split, as the batch's size query would.)
-            last = data[int(offs[-2]):] if chomp and offs.numel() > 1 else b""
+            last = data[int(offs[-2]):] if (chomp or field is not None) and offs.numel() > 1 else b""
             tail = bool(last) and len(last) not in model(last + b"\0")[:-1]
         trim = (len(rs) if rs is not None else 1) if chomp else 0
         with self._batch_actions_for_call(batch_actions):
-            out, ooff, status, fpos, fstage = self.run_batch_tensor(v, offs, trim=trim, last_whole=bool(trim and tail and data), suffix=ors)
+            if field is not None:
+                out, ooff, status, fpos, fstage = self.run_batch_fields_tensor(
+                    v, offs, field, fs, quote, escape, sep_len=len(rs) if rs is not None else 1, last_whole=bool(tail and data),
+                    keep_sep=not chomp, suffix=ors)
+            else:
+                out, ooff, status, fpos, fstage = self.run_batch_tensor(v, offs, trim=trim, last_whole=bool(trim and tail and data), suffix=ors)
         torch.cuda.synchronize(dev)
         ob = out.cpu().numpy().tobytes()
         ooff, status, fpos, fstage = ooff.tolist(), status.tolist(), fpos.tolist(), fstage.tolist()
-        return [MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]] for i in range(len(status))]
+        return [NoFieldError(fpos[i]) if status[i] == 2 else MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]]
+                for i in range(len(status))]
 
     def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None, batch_actions=True, rs=None, chomp=False,
-                       ors=b""):
+                       ors=b"", field=None, fs=b"\t"):
         """kx_run_records_fd: the stream on in_fd in record mode, outputs to out_fd, one line per rejected record to report_fd
         (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected.  With a `quote`
         byte, kx_run_records_fd_quoted: a separator inside quotes ends no record.  With an `escape` byte,
         kx_run_records_fd_escaped: an escaped byte is only data (with or without a quote).  With `rs` (1 to 8 bytes),
         kx_run_records_fd_rs: records end after the leftmost, non-overlapping copies of rs.  `batch_actions` as in run_records.  With
         `chomp` or a non-empty `ors`, kx_run_records_fd_opts: records run without their separator, `ors` after every accepted
-        record's output."""
+        record's output.  With `field`, kx_run_records_fd_fields: the program runs on field `field` of every record (fields end at
+        the live `fs` bytes), the rest of the record is copied; a record with fewer fields is reported and counts as rejected."""
         for name, fd in (("in_fd", in_fd), ("out_fd", out_fd), ("report_fd", report_fd)):
             if isinstance(fd, bool) or not isinstance(fd, int):
                 raise TypeError("run_records_fd: %s must be an int file descriptor, not %s" % (name, type(fd).__name__))
@@ -1199,14 +1361,19 @@ class Program:
         e = None if escape is None else _check_escape(escape, sep, quote)
         chomp, ors = _check_chomp(chomp), _check_ors(ors)
         mode, qi = _records_mode(q, e, rs), -1 if q is None else q
+        if field is not None:
+            field = _check_field(field)
+            f = _check_fs(fs, quote, escape, sep if rs is None else rs if len(rs) == 1 else None)
         st = KxRecordsStats()
         with self._batch_actions_for_call(batch_actions):
-            if chomp or ors:                             # the framing: only kx_run_records_fd_opts has it
+            if chomp or ors or field is not None:        # the framing: only kx_run_records_fd_opts (and _fields) has it
                 o = KxRecordsOpts(size=ctypes.sizeof(KxRecordsOpts), mode=mode, sep=s, quote=qi, escape=-1 if e is None else e,
                                   rs_len=len(rs or b""), chomp=1 if chomp else 0, ors_len=len(ors))
                 o.rs[:o.rs_len] = rs or b""
                 o.ors[:len(ors)] = ors
                 name, args = "kx_run_records_fd_opts", (ctypes.byref(o),)
+                if field is not None:
+                    name, args = "kx_run_records_fd_fields", (ctypes.byref(o), field, f)
             else:                                        # the mode's own entry point
                 name, args = (("kx_run_records_fd", (s,)), ("kx_run_records_fd_quoted", (s, q)), ("kx_run_records_fd_escaped", (s, qi, e)),
                               ("kx_run_records_fd_rs", (rs, len(rs or b""))))[mode]
