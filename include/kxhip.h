@@ -406,6 +406,55 @@ int kx_fields_stats(const kx_program* prog, kx_fields_kernel_stats* out);
 int kx_run_records_fd_fields(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, uint32_t field, uint8_t fs, int report_fd,
                              kx_records_stats* stats);
 
+/* ---- field mode with a list of fields: the program runs on every selected field of a record, the rest is copied ------------------
+ * kx_run_batch_field_list is kx_run_batch_fields in everything not said here: the records, their bodies, the live `fs` bytes, the
+ * field numbering, sep_len, last_whole, keep_sep and the suffix are the same.  The selected set S is the union of `ranges` (the
+ * NORMAL FORM of a `--field=LIST`: sorted, disjoint, not adjacent; hi = 0 means lo and every field behind it, and only the last
+ * range may be open).  `need` is the largest number S names explicitly: the largest closed bound, or the open range's lo.
+ *   record i with at least `need` fields: every field whose number is in S is run as a whole input of its own (every stage; its
+ *     result is kx_run_device's for those bytes alone; each field of a range is a document of its own, the fs bytes between them
+ *     are copied bytes).  If every one is accepted, the record's output is its body with every selected field replaced by the
+ *     program's output for it + its own separator (keep_sep != 0, and the record has one) + suffix; d_docs[i] = {0, 0, 0}.
+ *     Otherwise its output range is empty and d_docs[i] = {fail_pos, 1, fail_stage} of the LOWEST rejected field, fail_pos counted
+ *     inside that field.
+ *   record i with fewer than `need` fields: its output range is empty; d_docs[i] = {fields found, 2, 0}; the program runs on none
+ *     of its fields.  It counts as rejected.
+ * d_fail_field (a device array of n_docs uint32_t, or NULL): the field number K of the record's report line — the lowest rejected
+ * field, or the smallest member of S above the fields the record has — and 0 for an accepted record.  n_docs, d_docs, d_out_off,
+ * stats->docs and stats->docs_rejected count RECORDS; stats->docs_routed and docs_replayed are the inner kx_run_batch's and count
+ * field runs.  KX_E_ARG besides kx_run_batch_fields's (a wrong `size`, the quote, escape, fs, sep_len, suffix_len and reserved-word
+ * rules: before any device work; decreasing offsets and short ranges: on the device before any kernel reads a record): a list that
+ * is not in normal form or has no or more than 8 ranges (before any device work), and a call whose records select more than
+ * 2^32 - 2 fields in total (the inner batch's limit).  Per call the library holds 32 bytes of workspace per record, 64 per selected
+ * field, the selected fields' bytes and the program's output. */
+typedef struct kx_field_range { uint32_t lo, hi; } kx_field_range;   /* hi = 0: open (lo and everything behind it) */
+typedef struct kx_batch_field_list {
+  uint32_t size;         /* sizeof(kx_batch_field_list) */
+  uint32_t n_ranges;     /* 1 to 8 */
+  kx_field_range ranges[8];   /* the normal form: lo >= 1; hi == 0 or hi >= lo; ranges[j+1].lo > ranges[j].hi + 1; only the last may be open */
+  uint8_t fs;            /* the field separator */
+  uint8_t pad[3];        /* must be 0 */
+  int32_t quote;         /* a byte value, or -1: none */
+  int32_t escape;        /* a byte value, or -1: none */
+  uint32_t sep_len;      /* 0 to 8: the last sep_len bytes of every range are the record's separator */
+  uint32_t last_whole;   /* != 0: the last record has no separator */
+  uint32_t keep_sep;     /* != 0: a record's separator follows its output */
+  uint32_t suffix_len;   /* 0 to 8 */
+  uint8_t suffix[8];
+  uint32_t reserved[4];  /* must be 0 */
+} kx_batch_field_list;
+int kx_run_batch_field_list(kx_program* prog, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* list,
+                            void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs, uint32_t* d_fail_field, size_t* out_len,
+                            kx_batch_stats* stats, void* stream);
+
+/* kx_run_records_fd_fields with a list (`BIN --records … --field=LIST [--fs=F]`): every record goes through kx_run_batch_field_list
+ * with ranges[0, n_ranges) (the normal form, as above).  A record with too few fields reports "Record R has no field K!", a record
+ * with a rejected field reports ONCE, "Match error at input symbol S in field K of record R!" with K the lowest rejected field and
+ * S counted inside it; both write nothing and count in records_rejected.  KX_E_ARG: kx_run_records_fd_fields's, and a list that is
+ * not in normal form. */
+int kx_run_records_fd_field_list(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_field_range* ranges,
+                                 uint32_t n_ranges, uint8_t fs, int report_fd, kx_records_stats* stats);
+
 /* ---- sharded execution: one contiguous shard of the input per GPU -------------
  * Per stage and per rank:
  *   kx_shard_begin → kx_shard_forward → [exchange kx_fwd_summary] → kx_shard_fix_head

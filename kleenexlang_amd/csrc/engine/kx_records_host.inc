@@ -23,7 +23,8 @@
 //
 // Field mode (kx_run_records_fd_fields): RecordsRun::batch calls kx_run_batch_fields (kx_fields_host.inc) instead — the carried
 // record and the window's records alike — with the split's quote and escape byte, the separator's length and, unless `chomp`, the
-// separator kept behind the record's output.  A record without the field is reported in a line of its own kind.
+// separator kept behind the record's output.  A record without the field is reported in a line of its own kind.  With a list of
+// fields (kx_run_records_fd_field_list) it calls kx_run_batch_field_list the same way; the report lines name the field.
 
 namespace {
 
@@ -236,10 +237,13 @@ struct RecordsRun {
   kx_records_opts o{};                                 // the split, and the framing: chomp, ors (checkRecordsOpts has passed)
   uint32_t field = 0;                                  // field mode: the program runs on field `field` (0: on the record)
   uint8_t fsep = 0;                                    //   ... of the fields that `fsep` separates
+  kx_field_range ranges[8] = {};                       // field mode with a list: the program runs on the fields of ranges[0, n_ranges)
+  uint32_t n_ranges = 0;                               //   (0: no list; `field` is 0 with a list)
   SplitCarry next;                                     // what the next window's split starts from
   int report_fd = -1;
   RecWs ws;
   BatchWs::Buf off, ooff, docs, carry, one, longest;   // offsets; output offsets; doc records; the straddling record; its offsets
+  BatchWs::Buf ffield;                                 // with a list: the field number of every record's report line
   uint64_t carry_len = 0, recno = 0;                   // records reported so far (R of the next record is recno + 1)
   double ratio = 4.0;                                  // output bytes per input byte, from the previous window
   bool rejected = false;
@@ -248,15 +252,19 @@ struct RecordsRun {
   bool timing = false;
 
   ~RecordsRun() {
-    for (BatchWs::Buf* b : {&off, &ooff, &docs, &carry, &one, &longest}) if (b->p) (void)hipFree(b->p);
+    for (BatchWs::Buf* b : {&off, &ooff, &docs, &carry, &one, &longest, &ffield}) if (b->p) (void)hipFree(b->p);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
   }
 
-  int report(const kx_batch_doc* d, uint64_t n, uint64_t first_rec) {
+  // ff: with a list, the field number of every record's line
+  int report(const kx_batch_doc* d, uint64_t n, uint64_t first_rec, const uint32_t* ff = nullptr) {
     if (report_fd < 0) return 0;
     std::string s;
     for (uint64_t i = 0; i < n; ++i)
-      if (d[i].status == 2) s += "Record " + std::to_string(first_rec + i) + " has no field " + std::to_string(field) + "!\n";
+      if (d[i].status == 2) s += "Record " + std::to_string(first_rec + i) + " has no field " + std::to_string(ff ? ff[i] : field) + "!\n";
+      else if (d[i].status && ff)
+        s += "Match error at input symbol " + std::to_string(d[i].fail_pos) + " in field " + std::to_string(ff[i]) + " of record " +
+             std::to_string(first_rec + i) + "!\n";
       else if (d[i].status) s += "Match error at input symbol " + std::to_string(d[i].fail_pos) + " in record " + std::to_string(first_rec + i) + "!\n";
     for (size_t w = 0; w < s.size();) {
       const ssize_t r = write(report_fd, s.data() + w, s.size() - w);
@@ -286,12 +294,22 @@ struct RecordsRun {
     fl.keep_sep = o.chomp ? 0u : 1u;
     fl.suffix_len = o.ors_len;
     memcpy(fl.suffix, o.ors, o.ors_len);
+    kx_batch_field_list ll{};
+    ll.size = sizeof ll; ll.n_ranges = n_ranges; ll.fs = fsep;
+    memcpy(ll.ranges, ranges, sizeof ll.ranges);
+    ll.quote = fl.quote; ll.escape = fl.escape; ll.sep_len = fl.sep_len; ll.last_whole = fl.last_whole; ll.keep_sep = fl.keep_sep;
+    ll.suffix_len = fl.suffix_len;
+    memcpy(ll.suffix, fl.suffix, sizeof ll.suffix);
     auto run = [&](void* d_out, size_t cap, size_t* ol, kx_batch_stats* bs) {
+      if (n_ranges)
+        return kx_run_batch_field_list(p, in, d_o, ndocs, &ll, d_out, cap, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, (uint32_t*)ffield.p, ol, bs,
+                                       nullptr);
       return field ? kx_run_batch_fields(p, in, d_o, ndocs, &fl, d_out, cap, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, ol, bs, nullptr)
                    : kx_run_batch_framed(p, in, d_o, ndocs, frp, d_out, cap, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, ol, bs, nullptr);
     };
     int rc = BatchWs::ensure(ooff, (ndocs + 1) * 8);
     if (!rc) rc = BatchWs::ensure(docs, ndocs * sizeof(kx_batch_doc));
+    if (!rc && n_ranges) rc = BatchWs::ensure(ffield, ndocs * 4);
     if (rc) return rc;
     kx_batch_stats bs{};
     size_t ol = 0;
@@ -317,7 +335,9 @@ struct RecordsRun {
       st.records_rejected += bs.docs_rejected;
       std::vector<kx_batch_doc> h(ndocs);
       HIPCHECK(hipMemcpy(h.data(), docs.p, ndocs * sizeof(kx_batch_doc), hipMemcpyDeviceToHost));
-      return report(h.data(), ndocs, first_rec);
+      std::vector<uint32_t> hf(n_ranges ? ndocs : 0);
+      if (n_ranges) HIPCHECK(hipMemcpy(hf.data(), ffield.p, ndocs * 4, hipMemcpyDeviceToHost));
+      return report(h.data(), ndocs, first_rec, n_ranges ? hf.data() : nullptr);
     }
     return 0;
   }
@@ -519,7 +539,7 @@ int checkRecordsOpts(const kx_records_opts& o, const char* who, int fs = -1) {
 
 // the stream on in_fd in record mode as `o` says (checkRecordsOpts has passed)
 int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o, int report_fd, kx_records_stats* stats, uint32_t field = 0,
-                 uint8_t fsep = 0) {
+                 uint8_t fsep = 0, const kx_field_range* ranges = nullptr, uint32_t n_ranges = 0) {
   if (!p) return setErr(KX_E_ARG, "null argument");
   if (p->cfg.phase) return setErr(KX_E_ARG, "record mode runs every phase: kx_config::phase must be 0");
   const double t_begin = FdStream::nowMs();
@@ -533,6 +553,8 @@ int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o,
   (void)hipGetDevice(&fsr.dev);
   RecordsRun R;
   R.p = p; R.fs = &fsr; R.o = o; R.report_fd = report_fd; R.field = field; R.fsep = fsep;
+  R.n_ranges = n_ranges;
+  if (n_ranges) memcpy(R.ranges, ranges, n_ranges * sizeof(kx_field_range));
   R.timing = p->cfg.collect_timing != 0;
   int rc = 0;
   if (R.timing) for (auto& e : R.ev) if (hipEventCreate(&e) != hipSuccess) rc = setErr(KX_E_HIP, "hipEventCreate failed");
@@ -590,4 +612,13 @@ extern "C" int kx_run_records_fd_fields(kx_program* p, int in_fd, int out_fd, co
   if (field == 0) return setErr(KX_E_ARG, "kx_run_records_fd_fields: field numbers start at 1");
   if (const int rc = checkRecordsOpts(*o, "kx_run_records_fd_fields", fs)) return rc;
   return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, field, fs);
+}
+
+extern "C" int kx_run_records_fd_field_list(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_field_range* ranges,
+                                            uint32_t n_ranges, uint8_t fs, int report_fd, kx_records_stats* stats) {
+  if (!o || !ranges) return setErr(KX_E_ARG, "null argument");
+  if (!kxFieldListIsNormal(ranges, n_ranges))
+    return setErr(KX_E_ARG, "kx_run_records_fd_field_list: the field list is not in normal form (1 to 8 ranges: sorted, disjoint, not adjacent, only the last open)");
+  if (const int rc = checkRecordsOpts(*o, "kx_run_records_fd_field_list", fs)) return rc;
+  return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, 0, fs, ranges, n_ranges);
 }

@@ -19,7 +19,10 @@
 // record (kx_run_records_fd_opts): the framing is the command line's, the program sees only the record.  With `--field=K` the
 // program runs on field K of every record — the fields lie between the `--fs=F` bytes (default a tab) that the quote and the
 // escape rules leave live — and the rest of the record is copied around its output (kx_run_records_fd_fields); a record with
-// fewer fields writes nothing and is reported as "Record R has no field K!".  What --field and --fs refuse exits with status 2.
+// fewer fields writes nothing and is reported as "Record R has no field K!".  With `--field=LIST` (2,5-7,9-: anything but one
+// plain number) the program runs on every field of the list, each a whole input of its own, and the record is written only if all
+// of them are accepted (kx_run_records_fd_field_list; the list's parser is kx_field_list.h).  What --field and --fs refuse exits
+// with status 2.
 //
 // BIN = this executable ++ KXP blob ++ libdir ++ trailer (see kexc main.cpp).
 // The engine is loaded with dlopen so that this file carries no HIP dependency.
@@ -36,6 +39,7 @@
 #include <vector>
 
 #include "../../../include/kxhip.h"
+#include "kx_field_list.h"
 
 // The engine's switches are fields of kx_config (include/kxhip.h); the library reads no environment variable for them.  A produced
 // binary keeps honouring the variable names that earlier rounds' scripts use: they are read HERE, once, and mapped onto the struct.
@@ -83,6 +87,7 @@ static void usage(const char* name) {
   fprintf(stdout, "- \"%s --records ... --chomp\": every record is run without its separator (a last record without one is run whole).\n", name);
   fprintf(stdout, "- \"%s --records ... --ors=STR\": the 0 to 8 bytes STR spells follow the output of every accepted record.\n", name);
   fprintf(stdout, "- \"%s --records ... --field=K [--fs=F]\": runs field K (from 1; fields end at F, default a tab) of every record, the rest is copied.\n", name);
+  fprintf(stdout, "- \"%s --records ... --field=LIST [--fs=F]\": the same on every field of LIST (2,5-7,9-); a record is written only if all of them are accepted.\n", name);
 }
 
 // --records=SEP, --quote=Q, --escape=E: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
@@ -172,6 +177,8 @@ int main(int argc, char** argv) {
   uint8_t sep = '\n', quote = '"', escape = '\\', rs[8] = {}, ors[8] = {};
   uint32_t rs_len = 0, ors_len = 0, field = 0;
   bool field_given = false, fs_given = false;
+  kx_field_range ranges[KX_FIELD_RANGES] = {};   // --field=LIST in normal form (n_ranges = 0: --field=K, one plain number)
+  uint32_t n_ranges = 0;
   uint8_t fsep = '\t';
   long phase = 0, gpus = 0;
   int c;
@@ -212,6 +219,14 @@ int main(int argc, char** argv) {
         break;
       case 'f': {
         field_given = true;
+        n_ranges = 0; field = 0;
+        if (strpbrk(optarg, ",-")) {   // a list; one plain number (and what is neither) takes the single-field path below
+          if (const char* why = kxParseFieldList(optarg, ranges, &n_ranges)) {
+            fprintf(stderr, "Invalid --field: %s (a number from 1 to 4294967295, or a list such as 2,5-7,9-: %s)\n", optarg, why);
+            return 2;
+          }
+          break;
+        }
         char* end = nullptr;
         const unsigned long long v = (*optarg >= '0' && *optarg <= '9') ? strtoull(optarg, &end, 10) : 0;
         if (!end || *end || v < 1 || v > 0xFFFFFFFFull || strlen(optarg) > 10) { fprintf(stderr, "Invalid --field: %s (a number from 1 to 4294967295)\n", optarg); return 2; }
@@ -266,11 +281,13 @@ int main(int argc, char** argv) {
     decltype(&kx_run_records_fd_rs) runm = nullptr;
     decltype(&kx_run_records_fd_opts) runo = nullptr;
     decltype(&kx_run_records_fd_fields) runf = nullptr;
+    decltype(&kx_run_records_fd_field_list) runl = nullptr;
     if (!runr) return 1;
     if (quoted && !(runq = (decltype(runq))engineSymbol(h, argv[0], "kx_run_records_fd_quoted", "--quote needs"))) return 1;
     if (escaped && !(rune = (decltype(rune))engineSymbol(h, argv[0], "kx_run_records_fd_escaped", "--escape needs"))) return 1;
     if (multi && !(runm = (decltype(runm))engineSymbol(h, argv[0], "kx_run_records_fd_rs", "--rs needs"))) return 1;
-    if (field_given && !(runf = (decltype(runf))engineSymbol(h, argv[0], "kx_run_records_fd_fields", "--field needs"))) return 1;
+    if (field_given && !n_ranges && !(runf = (decltype(runf))engineSymbol(h, argv[0], "kx_run_records_fd_fields", "--field needs"))) return 1;
+    if (n_ranges && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_list", "--field=LIST needs"))) return 1;
     if (framing && !(runo = (decltype(runo))engineSymbol(h, argv[0], "kx_run_records_fd_opts", "--chomp and --ors need"))) return 1;
     // record mode is where the single-document route is unusable (a third of a millisecond per record): stages with register
     // actions are replayed by the batch kernels unless KX_BATCH_ACTIONS=0 asks for the route
@@ -288,7 +305,8 @@ int main(int argc, char** argv) {
       memcpy(o.rs, rs, 8); o.rs_len = rs_len;
       o.chomp = chomp ? 1u : 0u;
       memcpy(o.ors, ors, 8); o.ors_len = ors_len;
-      rc = field_given ? runf(prog, STDIN_FILENO, STDOUT_FILENO, &o, field, fsep, STDERR_FILENO, &rs_stats)
+      rc = n_ranges    ? runl(prog, STDIN_FILENO, STDOUT_FILENO, &o, ranges, n_ranges, fsep, STDERR_FILENO, &rs_stats)
+           : field_given ? runf(prog, STDIN_FILENO, STDOUT_FILENO, &o, field, fsep, STDERR_FILENO, &rs_stats)
                        : runo(prog, STDIN_FILENO, STDOUT_FILENO, &o, STDERR_FILENO, &rs_stats);
     } else if (multi) rc = runm(prog, STDIN_FILENO, STDOUT_FILENO, rs, rs_len, STDERR_FILENO, &rs_stats);
     else if (escaped) rc = rune(prog, STDIN_FILENO, STDOUT_FILENO, sep, quoted ? (int)quote : -1, escape, STDERR_FILENO, &rs_stats);

@@ -35,10 +35,11 @@ class EngineError(KleenexError):
 class MatchError(KleenexError):
     """The input is not in the program's language (reference: exit 1 + stderr message)."""
 
-    def __init__(self, pos, stage=0):
+    def __init__(self, pos, stage=0, field=None):
         super().__init__("Match error at input symbol %d!" % pos)
         self.pos = pos
         self.stage = stage
+        self.field = field      # field mode with a list: the number of the rejected field, `pos` counted inside it
 
 
 class NoFieldError(KleenexError):
@@ -433,6 +434,27 @@ class KxBatchFields(ctypes.Structure):
                 ("reserved", ctypes.c_uint32 * 4)]
 
 
+class KxFieldRange(ctypes.Structure):
+    """include/kxhip.h::kx_field_range (hi = 0: open)."""
+    _fields_ = [("lo", ctypes.c_uint32), ("hi", ctypes.c_uint32)]
+
+
+class KxBatchFieldList(ctypes.Structure):
+    """include/kxhip.h::kx_batch_field_list."""
+    _fields_ = [("size", ctypes.c_uint32), ("n_ranges", ctypes.c_uint32), ("ranges", KxFieldRange * 8), ("fs", ctypes.c_uint8),
+                ("pad", ctypes.c_uint8 * 3), ("quote", ctypes.c_int32), ("escape", ctypes.c_int32), ("sep_len", ctypes.c_uint32),
+                ("last_whole", ctypes.c_uint32), ("keep_sep", ctypes.c_uint32), ("suffix_len", ctypes.c_uint32),
+                ("suffix", ctypes.c_uint8 * 8), ("reserved", ctypes.c_uint32 * 4)]
+
+
+def _field_range_array(ranges):
+    """A normal form → (KxFieldRange * 8, n_ranges)."""
+    a = (KxFieldRange * 8)()
+    for j, (lo, hi) in enumerate(ranges):
+        a[j].lo, a[j].hi = lo, hi or 0
+    return a, len(ranges)
+
+
 class KxFieldsKernelStats(ctypes.Structure):
     """include/kxhip.h::kx_fields_kernel_stats."""
     _fields_ = [(k, ctypes.c_float) for k in ("locate_ms", "gather_ms", "scan_ms", "splice_ms")] + [("calls", ctypes.c_uint64)]
@@ -514,6 +536,135 @@ def field_records_model(data, offsets, sep_len, last_whole, field, fs, quote=Non
         lo = cuts[field - 2] + 1 if field > 1 else 0
         hi = cuts[field - 1] if len(cuts) >= field else len(body)
         res.append((body[:lo], body[lo:hi], body[hi:], sep))
+    return res
+
+
+FIELD_RANGES_MAX = 8
+
+
+def _normal_field_ranges(items, what):
+    """(lo, hi) pairs with hi None for an open range, each checked already → their normal form: the selected set as sorted,
+    disjoint, not adjacent ranges, a tuple of at most 8 pairs."""
+    top = 1 << 32                                               # (an open range's end: above every field number)
+    norm = []
+    for lo, hi in sorted((lo, top if hi is None else hi) for lo, hi in items):
+        if norm and lo <= norm[-1][1] + 1:
+            norm[-1][1] = max(norm[-1][1], hi)
+        else:
+            norm.append([lo, hi])
+    if len(norm) > FIELD_RANGES_MAX:
+        raise ValueError("%s: %d ranges in the normal form of the field list, at most %d" % (what, len(norm), FIELD_RANGES_MAX))
+    return tuple((lo, None if hi == top else hi) for lo, hi in norm)
+
+
+def parse_field_list(text):
+    """The LIST of `--field=LIST` → its normal form, a tuple of (lo, hi) pairs with hi None for an open range.  LIST is one or
+    more items joined by commas; an item is K, A-B (A <= B) or A- (A and every field behind it); a number has 1 to 10 decimal
+    digits and a value from 1 to 4294967295.  Items may come in any order and overlap: "3,2" → ((2, 3),), "4-,2,6" →
+    ((2, 2), (4, None)).  Raises ValueError for what the command line refuses: anything else, and a normal form of more than 8
+    ranges."""
+    if not isinstance(text, str):
+        raise TypeError("field list: a str such as '2,5-7,9-', not %s" % type(text).__name__)
+
+    def number(t):
+        if not (1 <= len(t) <= 10 and t.isascii() and t.isdigit() and 1 <= int(t) < 1 << 32):
+            raise ValueError("field list %r: %r is not a number from 1 to 4294967295" % (text, t))
+        return int(t)
+
+    items = []
+    for item in text.split(","):
+        a, dash, b = item.partition("-")
+        lo = number(a)
+        hi = lo if not dash else None if not b else number(b)
+        if hi is not None and hi < lo:
+            raise ValueError("field list %r: the range %s needs A <= B" % (text, item))
+        items.append((lo, hi))
+    return _normal_field_ranges(items, "field list %r" % text)
+
+
+def _check_field_ranges(fields):
+    """The `fields=` of record mode: a parse_field_list result, or a sequence of field numbers and (lo, hi) pairs (hi None: open)
+    → the normal form."""
+    if isinstance(fields, (str, bytes, bytearray)) or not isinstance(fields, (tuple, list)):
+        raise TypeError("fields: a parse_field_list result or a sequence of ints and (lo, hi) pairs, not %s" % type(fields).__name__)
+    if not fields:
+        raise ValueError("fields: an empty list selects nothing")
+    items = []
+    for it in fields:
+        if isinstance(it, (tuple, list)):
+            if len(it) != 2:
+                raise ValueError("fields: a range is a (lo, hi) pair, not %r" % (it,))
+            lo, hi = _check_field(it[0]), None if it[1] is None else _check_field(it[1])
+            if hi is not None and hi < lo:
+                raise ValueError("fields: the range %r needs lo <= hi" % (it,))
+        else:
+            lo = hi = _check_field(it)
+        items.append((lo, hi))
+    return _normal_field_ranges(items, "fields")
+
+
+def field_list_need(ranges):
+    """The largest field number a normal form names explicitly: a record with fewer fields runs nothing."""
+    lo, hi = ranges[-1]
+    return lo if hi is None else hi
+
+
+def field_list_missing(ranges, nfields):
+    """K of "Record R has no field K!": the smallest member of the list above the `nfields` fields a record has."""
+    for lo, hi in ranges:
+        if hi is None or hi > nfields:
+            return max(lo, nfields + 1)
+    raise ValueError("the list names no field above %d" % nfields)
+
+
+def field_list_records_model(data, offsets, sep_len, last_whole, ranges, fs, quote=None, escape=None):
+    """kx_run_batch_field_list's view of its records in pure Python — the normative model of `--field=LIST`.  The records, their
+    bodies, the live `fs` bytes and the field numbering are field_records_model's; `ranges` is the list (what `fields=` takes).  A
+    record with at least field_list_need(ranges) fields gives (gaps, fields, separator): with m selected fields, `fields` is m
+    pairs (K, bytes) in field order and `gaps` the m + 1 byte strings around them, so that the body is gaps[0] + fields[0][1] +
+    gaps[1] + … + gaps[m].  A record with fewer fields gives the number of fields it has."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError("field_list_records_model: data must be bytes, not %s" % type(data).__name__)
+    sep_len, ranges = _check_sep_len(sep_len), _check_field_ranges(ranges)
+    if not isinstance(last_whole, bool):
+        raise TypeError("field_list_records_model: last_whole must be True or False, not %s" % type(last_whole).__name__)
+    f = _check_fs(fs, quote, escape)
+    q = None if quote is None else _one_byte(quote, "quote character")
+    e = None if escape is None else _one_byte(escape, "escape character")
+    if q is not None and q == e:
+        raise ValueError("escape character: %r is also the quote character" % bytes([e]))
+    data, offs = bytes(data), [int(o) for o in offsets]
+    check_batch_offsets(offs, len(data))
+    need = field_list_need(ranges)
+    n, res = len(offs) - 1, []
+    for i in range(n):
+        t = 0 if last_whole and i == n - 1 else sep_len
+        if offs[i + 1] - offs[i] < t:
+            raise ValueError("field_list_records_model: record %d is shorter than its separator (%d)" % (i, t))
+        body, sep = data[offs[i]:offs[i + 1] - t], data[offs[i + 1] - t:offs[i + 1]]
+        cuts, parity, esc = [], 0, False                      # the positions of the live separators
+        for k, b in enumerate(body):
+            if esc:
+                esc = False
+            elif e is not None and b == e:
+                esc = True
+            elif q is not None and b == q:
+                parity ^= 1
+            elif b == f and parity == 0:
+                cuts.append(k)
+        nf = len(cuts) + 1
+        if nf < need:
+            res.append(nf)
+            continue
+        begin, end = [0] + [c + 1 for c in cuts], cuts + [len(body)]
+        gaps, fields, at = [], [], 0
+        for lo, hi in ranges:
+            for K in range(lo, (nf if hi is None else hi) + 1):
+                gaps.append(body[at:begin[K - 1]])
+                fields.append((K, body[begin[K - 1]:end[K - 1]]))
+                at = end[K - 1]
+        gaps.append(body[at:])
+        res.append((gaps, fields, sep))
     return res
 
 
@@ -686,6 +837,10 @@ def load_engine():
         lib.kx_run_batch_fields.argtypes = [vp, vp, vp, u64, ctypes.POINTER(KxBatchFields), vp, sz, vp, vp, ctypes.POINTER(sz),
                                             ctypes.POINTER(KxBatchStats), vp]
         lib.kx_fields_stats.argtypes = [vp, ctypes.POINTER(KxFieldsKernelStats)]
+        lib.kx_run_batch_field_list.argtypes = [vp, vp, vp, u64, ctypes.POINTER(KxBatchFieldList), vp, sz, vp, vp, vp, ctypes.POINTER(sz),
+                                                ctypes.POINTER(KxBatchStats), vp]
+        lib.kx_run_records_fd_field_list.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.POINTER(KxFieldRange),
+                                                     u32, ctypes.c_uint8, ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
         lib.kx_run_records_fd_fields.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), u32, ctypes.c_uint8,
                                                  ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
         lib.kx_run_records_fd_opts.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.c_int,
@@ -1140,8 +1295,9 @@ class Program:
         return self._run_batch_call("run_batch_tensor", values, offsets, out, frame, None)
 
     def _run_batch_call(self, what, values, offsets, out, frame, fields):
-        """The device part of run_batch_tensor (`frame`: a KxBatchFrame or None) and run_batch_fields_tensor (`fields`: a
-        KxBatchFields): the checks that need the tensors' device, the buffers, the size query and the call."""
+        """The device part of run_batch_tensor (`frame`: a KxBatchFrame or None), run_batch_fields_tensor (`fields`: a
+        KxBatchFields) and run_batch_field_list_tensor (`fields`: a KxBatchFieldList, which adds the fail_field tensor to the
+        result): the checks that need the tensors' device, the buffers, the size query and the call."""
         import torch
         if not values.is_cuda:
             raise EngineError("%s: values must be on a HIP device (there is no CPU fallback)" % what)
@@ -1156,6 +1312,8 @@ class Program:
         n = offsets.numel() - 1
         out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
         docs = torch.empty((max(n, 1), 2), dtype=torch.int64, device=dev)
+        listed = isinstance(fields, KxBatchFieldList)
+        ffield = torch.zeros(max(n, 1), dtype=torch.int32, device=dev) if listed else None
         stream = torch.cuda.current_stream(dev).cuda_stream
         vptr = values.data_ptr() if values.numel() else None
 
@@ -1164,7 +1322,12 @@ class Program:
             st = KxBatchStats()
             bptr = ctypes.c_void_p(buf.data_ptr() if buf is not None and buf.numel() else None)
             bcap = buf.numel() if buf is not None else 0
-            if fields is not None:
+            if listed:
+                rc = self._lib.kx_run_batch_field_list(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
+                                                       ctypes.byref(fields), bptr, bcap, ctypes.c_void_p(out_off.data_ptr()),
+                                                       ctypes.c_void_p(docs.data_ptr()), ctypes.c_void_p(ffield.data_ptr()),
+                                                       ctypes.byref(ol), ctypes.byref(st), ctypes.c_void_p(stream))
+            elif fields is not None:
                 rc = self._lib.kx_run_batch_fields(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
                                                    ctypes.byref(fields), bptr, bcap, ctypes.c_void_p(out_off.data_ptr()),
                                                    ctypes.c_void_p(docs.data_ptr()), ctypes.byref(ol), ctypes.byref(st),
@@ -1197,7 +1360,8 @@ class Program:
         if rc not in (0, 1):
             raise EngineError(self._err())
         d = docs[:n]
-        return out[:need], out_off, (d[:, 1] & 0xFFFFFFFF).to(torch.int32), d[:, 0], (d[:, 1] >> 32).to(torch.int32)
+        res = out[:need], out_off, (d[:, 1] & 0xFFFFFFFF).to(torch.int32), d[:, 0], (d[:, 1] >> 32).to(torch.int32)
+        return res + ((ffield[:n].to(torch.int64) & 0xFFFFFFFF),) if listed else res
 
     def run_batch_fields_tensor(self, values, offsets, field, fs=b"\t", quote=None, escape=None, sep_len=0, last_whole=False,
                                 keep_sep=True, suffix=b"", out=None):
@@ -1224,6 +1388,34 @@ class Program:
                              last_whole=1 if last_whole else 0, keep_sep=1 if keep_sep else 0, suffix_len=len(suffix))
         spec.suffix[:len(suffix)] = bytes(suffix)
         return self._run_batch_call("run_batch_fields_tensor", values, offsets, out, None, spec)
+
+    def run_batch_field_list_tensor(self, values, offsets, ranges, fs=b"\t", quote=None, escape=None, sep_len=0, last_whole=False,
+                                    keep_sep=True, suffix=b"", out=None):
+        """Field mode with a list (kx_run_batch_field_list): run_batch_fields_tensor where the program runs on every field of
+        `ranges` (a parse_field_list result, or a sequence of ints and (lo, hi) pairs), each a whole input of its own
+        (field_list_records_model).  A record with all its selected fields accepted writes its body with every one replaced by the
+        program's output, then separator and suffix as there.  Returns (out, out_off, status, fail_pos, fail_stage, fail_field):
+        status 1 = a field was rejected, fail_field[i] the lowest such and fail_pos[i] counted inside it; status 2 = the record
+        has too few fields, fail_pos[i] of them, and fail_field[i] is the first one it lacks; fail_field 0 = accepted."""
+        _check_batch_args(values, offsets)
+        ranges, sep_len = _check_field_ranges(ranges), _check_sep_len(sep_len)
+        f = _check_fs(fs, quote, escape)
+        q = -1 if quote is None else _one_byte(quote, "quote character")
+        e = -1 if escape is None else _one_byte(escape, "escape character")
+        if q >= 0 and q == e:
+            raise ValueError("escape character: %r is also the quote character" % bytes([e]))
+        for name, v in (("last_whole", last_whole), ("keep_sep", keep_sep)):
+            if not isinstance(v, bool):
+                raise TypeError("run_batch_field_list_tensor: %s must be True or False, not %s" % (name, type(v).__name__))
+        if not isinstance(suffix, (bytes, bytearray)):
+            raise TypeError("run_batch_field_list_tensor: suffix must be bytes of length 0 to 8, not %s" % type(suffix).__name__)
+        if len(suffix) > 8:
+            raise ValueError("run_batch_field_list_tensor: suffix must be 0 to 8 bytes, not %d" % len(suffix))
+        arr, nr = _field_range_array(ranges)
+        spec = KxBatchFieldList(size=ctypes.sizeof(KxBatchFieldList), n_ranges=nr, ranges=arr, fs=f, quote=q, escape=e, sep_len=sep_len,
+                                last_whole=1 if last_whole else 0, keep_sep=1 if keep_sep else 0, suffix_len=len(suffix))
+        spec.suffix[:len(suffix)] = bytes(suffix)
+        return self._run_batch_call("run_batch_field_list_tensor", values, offsets, out, None, spec)
 
     def fields_kernel_stats(self):
         """kx_fields_stats: HIP-event times of field mode's own kernels, summed over this program's calls (collect_timing)."""
@@ -1278,7 +1470,7 @@ class Program:
         return rs
 
     def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None, batch_actions=True, rs=None, chomp=False, ors=b"",
-                    field=None, fs=b"\t"):
+                    field=None, fs=b"\t", fields=None):
         """Record mode on bytes: every record of `data` (split after each `sep` byte, kx_split_records on the device) is a
         whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage).  With a `quote` byte
         a separator inside quotes ends no record (kx_split_records_quoted from parity 0).  With an `escape` byte an escaped
@@ -1290,12 +1482,19 @@ class Program:
         chomp_records_model).  With `field` (from 1) the program runs on that field of every record — the fields lie between the
         live `fs` bytes — and the rest of the record is copied around its output (kx_run_batch_fields, field_records_model): the
         separator is never part of the body, and follows the output unless `chomp`; a record with fewer fields gives a
-        NoFieldError."""
+        NoFieldError.  With `fields` (a parse_field_list result, or a sequence of ints and (lo, hi) pairs; not with `field`) the
+        program runs on every field of the list (kx_run_batch_field_list, field_list_records_model): a record with a rejected
+        field gives a MatchError whose `field` is the lowest rejected field and whose `pos` counts inside it."""
         if not isinstance(data, (bytes, bytearray, memoryview)):
             raise TypeError("run_records: data must be bytes, not %s" % type(data).__name__)
         chomp, ors = _check_chomp(chomp), _check_ors(ors)
+        if field is not None and fields is not None:
+            raise ValueError("run_records: field= and fields= exclude each other")
         if field is not None:
             field = _check_field(field)
+        if fields is not None:
+            fields = _check_field_ranges(fields)
+        if field is not None or fields is not None:
             _check_fs(fs, quote, escape, sep if rs is None else rs if len(rs) == 1 else None)
         if rs is not None:
             rs = self._check_rs_alone(rs, sep, quote, escape, "run_records")
@@ -1325,11 +1524,16 @@ class Program:
             # tail: the last record has no valid separator.  The record starts at a boundary, where the split's state is 0, so
             # the split model says it: with one more byte behind the record, its end is a boundary iff a separator ends it.
             # (`data` is bytes here, whatever came in; reading offs[-2] waits for the split, as the batch's size query would.)
-            last = data[int(offs[-2]):] if (chomp or field is not None) and offs.numel() > 1 else b""
+            last = data[int(offs[-2]):] if (chomp or field is not None or fields is not None) and offs.numel() > 1 else b""
             tail = bool(last) and len(last) not in model(last + b"\0")[:-1]
         trim = (len(rs) if rs is not None else 1) if chomp else 0
+        ffield = None
         with self._batch_actions_for_call(batch_actions):
-            if field is not None:
+            if fields is not None:
+                out, ooff, status, fpos, fstage, ffield = self.run_batch_field_list_tensor(
+                    v, offs, fields, fs, quote, escape, sep_len=len(rs) if rs is not None else 1, last_whole=bool(tail and data),
+                    keep_sep=not chomp, suffix=ors)
+            elif field is not None:
                 out, ooff, status, fpos, fstage = self.run_batch_fields_tensor(
                     v, offs, field, fs, quote, escape, sep_len=len(rs) if rs is not None else 1, last_whole=bool(tail and data),
                     keep_sep=not chomp, suffix=ors)
@@ -1338,11 +1542,12 @@ class Program:
         torch.cuda.synchronize(dev)
         ob = out.cpu().numpy().tobytes()
         ooff, status, fpos, fstage = ooff.tolist(), status.tolist(), fpos.tolist(), fstage.tolist()
-        return [NoFieldError(fpos[i]) if status[i] == 2 else MatchError(fpos[i], fstage[i]) if status[i] else ob[ooff[i]:ooff[i + 1]]
+        ffield = [None] * len(status) if ffield is None else ffield.tolist()
+        return [NoFieldError(fpos[i]) if status[i] == 2 else MatchError(fpos[i], fstage[i], ffield[i]) if status[i] else ob[ooff[i]:ooff[i + 1]]
                 for i in range(len(status))]
 
     def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None, batch_actions=True, rs=None, chomp=False,
-                       ors=b"", field=None, fs=b"\t"):
+                       ors=b"", field=None, fs=b"\t", fields=None):
         """kx_run_records_fd: the stream on in_fd in record mode, outputs to out_fd, one line per rejected record to report_fd
         (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected.  With a `quote`
         byte, kx_run_records_fd_quoted: a separator inside quotes ends no record.  With an `escape` byte,
@@ -1350,7 +1555,9 @@ class Program:
         kx_run_records_fd_rs: records end after the leftmost, non-overlapping copies of rs.  `batch_actions` as in run_records.  With
         `chomp` or a non-empty `ors`, kx_run_records_fd_opts: records run without their separator, `ors` after every accepted
         record's output.  With `field`, kx_run_records_fd_fields: the program runs on field `field` of every record (fields end at
-        the live `fs` bytes), the rest of the record is copied; a record with fewer fields is reported and counts as rejected."""
+        the live `fs` bytes), the rest of the record is copied; a record with fewer fields is reported and counts as rejected.
+        With `fields` (as in run_records; not with `field`), kx_run_records_fd_field_list: the program runs on every field of the
+        list, and a record with a rejected field is reported once, with the field's number."""
         for name, fd in (("in_fd", in_fd), ("out_fd", out_fd), ("report_fd", report_fd)):
             if isinstance(fd, bool) or not isinstance(fd, int):
                 raise TypeError("run_records_fd: %s must be an int file descriptor, not %s" % (name, type(fd).__name__))
@@ -1361,12 +1568,17 @@ class Program:
         e = None if escape is None else _check_escape(escape, sep, quote)
         chomp, ors = _check_chomp(chomp), _check_ors(ors)
         mode, qi = _records_mode(q, e, rs), -1 if q is None else q
+        if field is not None and fields is not None:
+            raise ValueError("run_records_fd: field= and fields= exclude each other")
         if field is not None:
             field = _check_field(field)
+        if fields is not None:
+            fields = _check_field_ranges(fields)
+        if field is not None or fields is not None:
             f = _check_fs(fs, quote, escape, sep if rs is None else rs if len(rs) == 1 else None)
         st = KxRecordsStats()
         with self._batch_actions_for_call(batch_actions):
-            if chomp or ors or field is not None:        # the framing: only kx_run_records_fd_opts (and _fields) has it
+            if chomp or ors or field is not None or fields is not None:   # the framing: only kx_run_records_fd_opts (and _fields, _field_list) has it
                 o = KxRecordsOpts(size=ctypes.sizeof(KxRecordsOpts), mode=mode, sep=s, quote=qi, escape=-1 if e is None else e,
                                   rs_len=len(rs or b""), chomp=1 if chomp else 0, ors_len=len(ors))
                 o.rs[:o.rs_len] = rs or b""
@@ -1374,6 +1586,9 @@ class Program:
                 name, args = "kx_run_records_fd_opts", (ctypes.byref(o),)
                 if field is not None:
                     name, args = "kx_run_records_fd_fields", (ctypes.byref(o), field, f)
+                if fields is not None:
+                    arr, nr = _field_range_array(fields)
+                    name, args = "kx_run_records_fd_field_list", (ctypes.byref(o), arr, nr, f)
             else:                                        # the mode's own entry point
                 name, args = (("kx_run_records_fd", (s,)), ("kx_run_records_fd_quoted", (s, q)), ("kx_run_records_fd_escaped", (s, qi, e)),
                               ("kx_run_records_fd_rs", (rs, len(rs or b""))))[mode]
