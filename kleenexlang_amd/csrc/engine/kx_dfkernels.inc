@@ -2,11 +2,13 @@
 // kx_engine.hip inside its anonymous namespace, behind k_emit (it shares put_bytes, wave_scan_incl, load_piece, …).
 //
 //   k_dforward  lane = segment (as k_forward): the product state sequence from the segment's synchronisation point; per 64-byte
-//               piece one 16-byte record {state entering the piece, state in its middle, output bytes of the block before the
-//               piece, output bytes of the piece's first half}; per block the output bytes of its two parts
+//               piece one 8-byte record {state entering the piece, state in its middle, output bytes of the piece and of its
+//               first half, constants of either half} (DfRec); per 32 pieces one word: the output bytes of the block part before
+//               the first of them (the WAVE BASE array); per block the output bytes of its two parts
 //   k_dlen      block length = own part + spill part; the existing k_scan_* turn them into offsets
 //   k_demit     lane = piece, persistent: ONE forward walk per piece that places the output as it goes (two chains, from the
-//               two recorded states, write cursors running UP from the piece's known output offset); staging, constants as
+//               two recorded states, write cursors running UP from the piece's output offset = the wave-iteration's base + the
+//               prefix sum of the lengths of the pieces before it in the wave: the output is contiguous); staging, constants as
 //               jobs and the flush are k_emit's
 // Table image in LDS (address 0): class*8 u8[256] (class index where class*8 does not fit: DfDev::wide) | rows of C x {lo, hi}: lo = handle of the next state (its row's LDS address),
 // hi = what this step writes, in the layout of a path entry of the general engine's `direct` form: bit 0 "no input byte
@@ -34,10 +36,68 @@ struct DfDev {
 };
 // A piece that the slow path resolved has no states to walk from: its record names a run of SIDE ENTRIES instead (one per path
 // step: bit 0 copy, bits 1-30 the constant (>= sl_npc: none), bit 31 an entry without an input byte — a constant that was due),
-// and k_demit's lane replays them straight into the output (record: hh = index of the first entry, kc = DFREC_HOLE | first << 15 | entries).
-constexpr uint32_t DFREC_HOLE = 0xFFFF0000u, DF_HOLE_MAX = 4096, DF_HOLE_FIRST = 1024, DF_SL_LEAVES = 32;
-struct __attribute__((aligned(16))) DfRec { uint32_t hh, cum, info, kc; };   // hh = start | middle << 16; info = bytes of the first half | own << 31
-constexpr uint32_t DFREC_OWN = 0x80000000u;
+// and k_demit's lane replays them straight into the output (a hole record, below).
+constexpr uint32_t DF_HOLE_MAX = 4096, DF_HOLE_FIRST = 1024, DF_SL_LEAVES = 32;
+// THE PIECE RECORD, 8 bytes.  The widths are the image's own limits (kx_delayed.h; dfRecFits checks them when a stage is loaded):
+//   row handles   multiples of 8 below 64 KiB (rows of C x 8 bytes behind the 256-byte class table): handle >> 3 in 13 bits
+//   len, lenA     bytes appended by the piece / by its first half: a step appends at most DF_STEP_MAX = 126 bytes (the entry's
+//                 7-bit field, 127 never built), so len <= 64 * 126 fits 13 bits and lenA <= 32 * 126 fits 12
+//   kA, kB        constants of the first / second half: at most 32 each, 6 bits
+//   x = start >> 3 | middle >> 3 << 13 | kA << 26          y = len | lenA << 13 | kB << 25 | hole << 31
+// A hole record:  x = index of the piece's first side entry       y = len (16 bits) | entries << 16 (14 bits) | first << 30 | 1 << 31
+// (first: the first piece of a stretch, which also writes the K pending steps).  A piece has at most 64 + DF_MAX_K + (constants
+// due) entries; a stretch with a piece beyond 16 bits of output or 14 bits of entries is "not resolvable here".
+// Where a piece's output starts is not in its record: the output is contiguous, so k_demit adds up the lengths of the pieces in
+// front of it in its wave-iteration, from ONE absolute offset per iteration: wbase[piece / 32] = the block-relative offset of
+// every 32nd piece (bytes its block part — own or spill — holds before it) | DFREC_OWN if that part is the block's own.
+struct __attribute__((aligned(8))) DfRec { uint32_t x, y; };
+constexpr uint32_t DFREC_OWN = 0x80000000u, DFREC_HOLE = 0x80000000u, DFREC_HOLE_FIRST = 0x40000000u;
+constexpr uint32_t DF_MERGE_WINDOW_MAX = 64;   // the largest kx_config::merge_window (window J + 1)
+constexpr uint32_t DF_STEP_MAX = 126, DF_HOLE_LEN_MAX = 0xFFFFu, DF_HOLE_CNT_MAX = 0x3FFFu, DF_WBASE_PIECES = 32;
+constexpr DfRec dfrec_pack(uint32_t start, uint32_t middle, uint32_t lenA, uint32_t len, uint32_t kA, uint32_t kB) {
+  return DfRec{(start >> 3) | ((middle >> 3) << 13) | (kA << 26), len | (lenA << 13) | (kB << 25)};
+}
+constexpr DfRec dfrec_pack_hole(uint32_t side_first, uint32_t entries, bool first, uint32_t len) {
+  return DfRec{side_first, len | (entries << 16) | (first ? DFREC_HOLE_FIRST : 0u) | DFREC_HOLE};
+}
+constexpr bool dfrec_hole(DfRec r) { return (r.y & DFREC_HOLE) != 0; }
+constexpr uint32_t dfrec_start(DfRec r) { return (r.x & 0x1FFFu) << 3; }
+constexpr uint32_t dfrec_middle(DfRec r) { return ((r.x >> 13) & 0x1FFFu) << 3; }
+constexpr uint32_t dfrec_kA(DfRec r) { return r.x >> 26; }
+constexpr uint32_t dfrec_kB(DfRec r) { return (r.y >> 25) & 0x3Fu; }
+constexpr uint32_t dfrec_len(DfRec r) { return r.y & 0x1FFFu; }
+constexpr uint32_t dfrec_lenA(DfRec r) { return (r.y >> 13) & 0xFFFu; }
+constexpr uint32_t dfrec_hole_side(DfRec r) { return r.x; }
+constexpr uint32_t dfrec_hole_len(DfRec r) { return r.y & DF_HOLE_LEN_MAX; }
+constexpr uint32_t dfrec_hole_entries(DfRec r) { return (r.y >> 16) & DF_HOLE_CNT_MAX; }
+constexpr bool dfrec_hole_first(DfRec r) { return (r.y & DFREC_HOLE_FIRST) != 0; }
+namespace dfrec_check {
+constexpr uint32_t H = 65536 - 8, LA = HALF * DF_STEP_MAX, LN = PIECE * DF_STEP_MAX, KH = HALF;
+constexpr DfRec top = dfrec_pack(H, H, LA, LN, KH, KH), one = dfrec_pack(8, 65536 - 16, 1, 2, 0, KH), zero = dfrec_pack(0, 0, 0, 0, 0, 0);
+static_assert(sizeof(DfRec) == 8 && LN < (1u << 13) && LA < (1u << 12) && KH < (1u << 6), "piece record: a field outgrew its width");
+static_assert(!dfrec_hole(top) && dfrec_start(top) == H && dfrec_middle(top) == H && dfrec_lenA(top) == LA && dfrec_len(top) == LN &&
+              dfrec_kA(top) == KH && dfrec_kB(top) == KH, "piece record: every field at its maximum");
+static_assert(!dfrec_hole(one) && dfrec_start(one) == 8 && dfrec_middle(one) == 65536 - 16 && dfrec_lenA(one) == 1 && dfrec_len(one) == 2 &&
+              dfrec_kA(one) == 0 && dfrec_kB(one) == KH, "piece record: neighbouring fields do not bleed");
+static_assert(!dfrec_hole(zero) && zero.x == 0 && zero.y == 0, "piece record: all fields zero");
+constexpr DfRec htop = dfrec_pack_hole(0xFFFFFFFFu, DF_HOLE_CNT_MAX, true, DF_HOLE_LEN_MAX), hlow = dfrec_pack_hole(0, 0, false, 0);
+static_assert(dfrec_hole(htop) && dfrec_hole_side(htop) == 0xFFFFFFFFu && dfrec_hole_entries(htop) == DF_HOLE_CNT_MAX && dfrec_hole_first(htop) &&
+              dfrec_hole_len(htop) == DF_HOLE_LEN_MAX, "hole record: every field at its maximum");
+static_assert(dfrec_hole(hlow) && dfrec_hole_side(hlow) == 0 && dfrec_hole_entries(hlow) == 0 && !dfrec_hole_first(hlow) && dfrec_hole_len(hlow) == 0, "hole record: all fields zero");
+// entries of a piece: its 64 steps; the first piece of a stretch adds the K pending steps and the constants its state has due.  A
+// constant waits at most J steps (J = kx_config::merge_window - 1 <= DF_MERGE_WINDOW_MAX - 1, checkConfig) and at most one joins per
+// step: at most DF_MERGE_WINDOW_MAX are due.  (The 16-byte record had 15 bits for this count; 14 hold it with room to spare, and the
+// slow path checks the count of every piece it records all the same.)
+static_assert(PIECE + kxdf::DF_MAX_K + DF_MERGE_WINDOW_MAX <= DF_HOLE_CNT_MAX, "hole record: the entries of a piece fit");
+static_assert((uint64_t)MAX_SEG * DF_STEP_MAX < DFREC_OWN, "wave base: a block part's output stays below the own flag");
+static_assert(DF_WBASE_PIECES == HALF && 2 * DF_WBASE_PIECES == PIECE, "wave base: one word per wave-iteration of half pieces, two per iteration of pieces");
+}  // namespace dfrec_check
+// does a table image respect the record's widths?  (host side, at load: a stage whose image does not has no delayed form)
+inline bool dfRecFits(const uint32_t* img, uint32_t nrows, uint32_t C) {
+  if (256u + (uint64_t)nrows * C * 8u > 65536u) return false;          // every row handle below 64 KiB (and a multiple of 8 by construction)
+  for (size_t i = 0; i < (size_t)nrows * C; ++i) if ((img[64 + 2 * i + 1] >> 24) > DF_STEP_MAX) return false;
+  return true;
+}
 
 struct DfLds {
   const uint8_t* base; uint32_t csh;
@@ -264,13 +324,14 @@ __device__ __noinline__ int df_slow_resolve(DfSlowIO& io, const DfDev& D) {
 template <int BT, uint32_t DF_STAGE, int MINW, bool SLOW>
 __global__ __launch_bounds__(BT, MINW) void k_dforward(const uint8_t* __restrict__ in, uint64_t n, uint64_t seg, uint32_t nseg, int first_known,
                            const uint64_t* __restrict__ seg_pos, const uint16_t* __restrict__ seg_state,
-                           DfRec* __restrict__ rec, uint32_t* __restrict__ own, uint32_t* __restrict__ spill, Flags* flags,
+                           DfRec* __restrict__ rec, uint32_t* __restrict__ wbase, uint32_t* __restrict__ own, uint32_t* __restrict__ spill, Flags* flags,
                            uint32_t* __restrict__ side, uint32_t side_cap, int is_last, DfDev D) {
+  static_assert(DF_STAGE == 8 || DF_STAGE == 16, "a group of staged records is one or half a 128-byte line, and at least the slow path's 64-byte map");
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   DfLds L = df_stage(D, smem);
-  // per-lane staging of DF_STAGE piece records: they leave as whole lines (scattered 16-byte stores of lanes that are a
+  // per-lane staging of DF_STAGE piece records: they leave as whole lines (scattered 8-byte stores of lanes that are a
   // segment apart are read-modify-writes in L2)
-  uint4* lrec = reinterpret_cast<uint4*>(smem + ((D.words + 3) & ~3u)) + (size_t)threadIdx.x * DF_STAGE;
+  uint2* lrec = reinterpret_cast<uint2*>(smem + ((D.words + 3) & ~3u)) + (size_t)threadIdx.x * DF_STAGE;
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t lane = threadIdx.x & 63;
   const uint64_t B = k < nseg ? df_own_start(k, n, seg, first_known, seg_pos, seg_state, D) : UNSYNC;
@@ -322,35 +383,47 @@ __global__ __launch_bounds__(BT, MINW) void k_dforward(const uint8_t* __restrict
     failed = true;
     return 1;
   };
-  // records are staged in the slot (piece & 7) and leave when their group of 8 is complete (or the lane's part ends)
+  // records are staged in the slot (piece & (DF_STAGE - 1)) and leave when their group of DF_STAGE is complete (or the lane's part ends)
   uint32_t nst = 0; uint64_t gfirst = 0;
   auto flush_group = [&]() {
-    uint4* dst = reinterpret_cast<uint4*>(rec + gfirst);
+    // (as one 8-byte vector store each: stored field by field through the record type, this loop cost the ARMED instance's trips 38
+    //  scratch operations per step — 114 spilled registers instead of 70, its forward pass 4.2 -> 5.4 ms on a log with escaped quotes)
+    uint2* dst = reinterpret_cast<uint2*>(rec + gfirst);
     for (uint32_t i = 0; i < nst; ++i) dst[i] = lrec[(gfirst + i) & (DF_STAGE - 1)];
     nst = 0;
   };
   const bool coop = !(D.debug & 256u);   // (kx_config::debug_flags & 256: every lane flushes its own records — the A/B of profiles/r06_experiments.md)
   bool in_trip = false;   // inside a trip the complete groups leave together, cooperatively (coop_flush); elsewhere a lane flushes its own
-  auto stage_rec = [&](uint64_t pc, uint4 r) {
+  auto stage_rec = [&](uint64_t pc, DfRec r) {
     if (nst == 0) gfirst = pc;
-    lrec[pc & (DF_STAGE - 1)] = r; ++nst;
+    if ((pc & (DF_WBASE_PIECES - 1)) == 0) wbase[pc / DF_WBASE_PIECES] = cum | flag;   // (cum: still without this piece)
+    lrec[pc & (DF_STAGE - 1)] = make_uint2(r.x, r.y); ++nst;
     if (!in_trip && (pc & (DF_STAGE - 1)) == DF_STAGE - 1) flush_group();
   };
-  // Round 6: the complete record groups of a wave leave as WHOLE LINES written by DF_STAGE adjacent lanes each (lane l: record l % DF_STAGE
-  // of the group of lane (l / DF_STAGE) * DF_STAGE + i), instead of DF_STAGE 16-byte stores per lane that each touch 64 different lines:
-  // an eighth of the write requests (the same LDS reads; the groups' positions travel by two shuffles per step).  Only lanes whose group
-  // is complete take part as sources (a lane that died in mid-trip keeps its partial group for its own flush).
-  uint4* const lrec_wave = reinterpret_cast<uint4*>(smem + ((D.words + 3) & ~3u)) + (size_t)(threadIdx.x & ~63u) * DF_STAGE;
+  // a trip of eight pieces may start where the staged group is an aligned one: it then completes at the end of a trip (of every second
+  // trip with 16 staged records: the group survives the trip boundary in between) and leaves cooperatively
+  auto group_aligned = [&]() { return ((uint32_t)(pos >> 6) & (DF_STAGE - 1)) == nst; };
+  // Round 6: the complete record groups of a wave leave as WHOLE LINES written by adjacent lanes (teams of eight lanes; step i: the team
+  // writes the group of its lane i, every lane DF_STAGE / 8 records of it — with 16 staged records 16 bytes per lane, one 128-byte line
+  // per team and instruction; with 8, half a line), instead of DF_STAGE 8-byte stores per lane that each touch 64 different lines:
+  // a sixteenth of the write requests, and half of what the 16-byte records took per piece (the groups' positions travel by two
+  // shuffles per step).  Only lanes whose group is complete take part as sources (a lane that died in mid-trip keeps its partial
+  // group for its own flush).
+  uint2* const lrec_wave = reinterpret_cast<uint2*>(smem + ((D.words + 3) & ~3u)) + (size_t)(threadIdx.x & ~63u) * DF_STAGE;
   auto coop_flush = [&]() {
     const bool full = nst == DF_STAGE && (gfirst & (DF_STAGE - 1)) == 0;
+    if (!__any(full)) return;
     const uint32_t glo = (uint32_t)gfirst, ghi = (uint32_t)(gfirst >> 32) | (full ? 0u : 0x80000000u);
-    const uint32_t team = lane / DF_STAGE * DF_STAGE, r = lane % DF_STAGE;
-    static_for<0, (int)DF_STAGE>([&](auto ic) {
+    constexpr uint32_t RPL = DF_STAGE / 8;   // records per lane and store
+    const uint32_t team = lane & ~7u, r = (lane & 7u) * RPL;
+    static_for<0, 8>([&](auto ic) {
       constexpr uint32_t i = decltype(ic)::value;
       const uint32_t slo = (uint32_t)__shfl((int)glo, (int)(team + i)), shi = (uint32_t)__shfl((int)ghi, (int)(team + i));
       if (!(shi & 0x80000000u)) {
         const uint64_t g = ((uint64_t)shi << 32) | slo;
-        reinterpret_cast<uint4*>(rec + g)[r] = lrec_wave[(size_t)(team + i) * DF_STAGE + r];
+        const uint2* src = lrec_wave + (size_t)(team + i) * DF_STAGE + r;
+        if constexpr (RPL == 2) *reinterpret_cast<uint4*>(rec + g + r) = *reinterpret_cast<const uint4*>(src);
+        else *reinterpret_cast<uint2*>(rec + g + r) = *src;
       }
     });
     if (full) nst = 0;
@@ -395,8 +468,9 @@ __global__ __launch_bounds__(BT, MINW) void k_dforward(const uint8_t* __restrict
         const uint32_t ee = E[idx + x], pc = (ee >> 1) & 0x3FFFFFFFu;
         len += (ee & 1u) + (pc < D.sl_npc ? D.sl_pcoff[pc + 1] - D.sl_pcoff[pc] : 0u);
       }
-      if (len > 0xFFFFu) return 1;
-      rec[pp >> 6] = DfRec{base + idx, cum, len | flag, DFREC_HOLE | (first ? 0x8000u : 0u) | cnt};
+      if (len > DF_HOLE_LEN_MAX || cnt > DF_HOLE_CNT_MAX) return 1;
+      if (((pp >> 6) & (DF_WBASE_PIECES - 1)) == 0) wbase[(pp >> 6) / DF_WBASE_PIECES] = cum | flag;
+      rec[pp >> 6] = dfrec_pack_hole(base + idx, cnt, first, len);
       idx += cnt; cum += len; pos = pp + steps;
     }
     h = io.h_next;
@@ -424,7 +498,7 @@ __global__ __launch_bounds__(BT, MINW) void k_dforward(const uint8_t* __restrict
     }
     const uint32_t kA = (sumA & 0xFFu) >> 2, kB = (sum & 0xFFu) >> 2;
     kc_sum += kA + kB; kc_max = kA + kB > kc_max ? kA + kB : kc_max; ++kc_n;
-    stage_rec(pos >> 6, make_uint4(h0 | (mid << 16), cum, (sumA >> 8) | flag, kA | (kB << 8)));
+    stage_rec(pos >> 6, dfrec_pack(h0, mid, sumA >> 8, sum >> 8, kA, kB));
     cum += sum >> 8; pos += PIECE;
     return true;
   };
@@ -435,11 +509,11 @@ __global__ __launch_bounds__(BT, MINW) void k_dforward(const uint8_t* __restrict
   };
   for (;;) {   // (a lane that left a trip for the slow path stands on a piece boundary that is no trip boundary: resolve, align, go again)
   if (need_slow) run_slow();
-  while (!failed && !need_slow && pos + PIECE <= end && (pos & (8 * PIECE - 1))) single_piece();   // up to the next 512-byte boundary
+  while (!failed && !need_slow && pos + PIECE <= end && ((pos & (8 * PIECE - 1)) || !group_aligned())) single_piece();   // up to the next 512-byte boundary with an aligned group
   // trips of eight pieces with cooperative loads (k_forward's scheme): every 8 lanes fetch one 128-byte line of one lane's
   // segment per instruction, an 8 x 8 register transpose hands each lane its own line
   for (;;) {
-    const bool can = !failed && !need_slow && pos + 8 * PIECE <= end && !(pos & (8 * PIECE - 1));
+    const bool can = !failed && !need_slow && pos + 8 * PIECE <= end && !(pos & (8 * PIECE - 1)) && group_aligned();
     // (a lane that waits for the slow path leaves the trips with its whole wave: it would otherwise sit out every remaining trip of
     //  the others and then run its own alone — twice the wave's time for one undecided context, measured)
     if (!__any(can) || __any(need_slow)) break;
@@ -474,8 +548,8 @@ __global__ __launch_bounds__(BT, MINW) void k_dforward(const uint8_t* __restrict
       if (go && !do_piece(wa)) { died = true; go = false; }
       if (k2 < 3) issue(k2 + 1, v);
       if (go && !do_piece(wb)) died = true;
-      if (coop && ((k2 + 1) * 2) % DF_STAGE == 0) coop_flush();   // (wave-uniform: the lanes of a trip stage in lock-step)
     }
+    if (coop) coop_flush();   // (wave-uniform; the lanes whose group of 8 or 16 is complete: with 16, the lanes in the second trip of their group)
     in_trip = false;
   }
   if (!__any(!failed && (need_slow || pos + 8 * PIECE <= end))) break;
@@ -498,7 +572,7 @@ __global__ __launch_bounds__(BT, MINW) void k_dforward(const uint8_t* __restrict
     if (h == dead || h == esc) {
       if (fail_in(h0, pos, plen) == 2) { h = h0; need_slow = true; continue; }
     }
-    else { stage_rec(pos >> 6, make_uint4(h0 | (mid << 16), cum, lenA | flag, kA | ((kc - kA) << 8))); cum += len; pos = end; }
+    else { stage_rec(pos >> 6, dfrec_pack(h0, mid, lenA, len, kA, kc - kA)); cum += len; pos = end; }
   }
   break;
   }
@@ -511,7 +585,7 @@ __global__ __launch_bounds__(BT, MINW) void k_dforward(const uint8_t* __restrict
 
 // sharded runs: the bytes before the first lane's own part, from the state the previous shard ends in (one lane)
 __global__ void k_dhead(const uint8_t* __restrict__ in, uint64_t n, uint64_t seg, uint64_t head_len, uint32_t h,
-                        DfRec* __restrict__ rec, uint32_t* __restrict__ own, uint32_t* __restrict__ spill, Flags* flags, DfDev D) {
+                        DfRec* __restrict__ rec, uint32_t* __restrict__ wbase, uint32_t* __restrict__ own, uint32_t* __restrict__ spill, Flags* flags, DfDev D) {
   extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
   DfLds L = df_stage(D, smem);
   if (blockIdx.x || threadIdx.x) return;
@@ -533,7 +607,8 @@ __global__ void k_dhead(const uint8_t* __restrict__ in, uint64_t n, uint64_t seg
     }
     if (plen <= HALF) { mid = h; lenA = len; kA = kc; }
     if (kc > 0) atomicMax(&flags->emit_kmax, kc);
-    rec[pos >> 6] = DfRec{h0 | (mid << 16), cum, lenA, kA | ((kc - kA) << 8)};
+    if (((pos >> 6) & (DF_WBASE_PIECES - 1)) == 0) wbase[(pos >> 6) / DF_WBASE_PIECES] = cum;   // (a spill part: no own flag)
+    rec[pos >> 6] = dfrec_pack(h0, mid, lenA, len, kA, kc - kA);
     cum += len; pos += plen;
   }
   spill[m] = cum;
@@ -665,7 +740,7 @@ __device__ __forceinline__ void df_step_gen(uint32_t& h, uint32_t byte_now, uint
 // lane at work over half the input (iso_datetime_to_json: 265 output bytes per piece, three rounds of 22 lanes before)
 template <int WAVES, int K, bool HALF = false>
 __global__ __launch_bounds__(WAVES * 64) void k_demit(const uint8_t* __restrict__ in, uint64_t n, uint64_t blk, uint64_t blk_inv,
-                                                      uint64_t npieces_total, const DfRec* __restrict__ rec,
+                                                      uint64_t npieces_total, const DfRec* __restrict__ rec, const uint32_t* __restrict__ wbase,
                                                       const uint32_t* __restrict__ spill, const unsigned long long* __restrict__ off,
                                                       Flags* __restrict__ flags, uint32_t stgb, uint32_t jbytes, uint32_t maxcnt,
                                                       uint8_t* __restrict__ out, const uint32_t* __restrict__ side, DfDev D) {
@@ -682,9 +757,22 @@ __global__ __launch_bounds__(WAVES * 64) void k_demit(const uint8_t* __restrict_
   const uint64_t oend_all = flags->total_len;
   const uint64_t one_piece_blocks = (uint64_t)__builtin_amdgcn_readfirstlane(blk == (uint64_t)PIECE ? 1 : 0);
   // everything a unit needs is requested ONE ITERATION AHEAD (the walk needs the output offset at its first step)
-  struct Operands { uint32_t w[NW]; uint32_t wp; uint4 r; uint64_t off0; uint32_t sp0; uint4 r1; uint64_t off1; uint32_t sp1; };
+  // (the unit's own: its input words, the four bytes before them and its record; the wave's: where the output of the iteration's first
+  //  unit starts — base word, block offset and spill length of that unit's block, one address each for the whole wave)
+  struct Operands { uint32_t w[NW]; uint32_t wp; uint2 r; uint32_t wb; uint64_t off0; uint32_t sp0; };
   auto request = [&](uint64_t it_, Operands& o) {
     if (it_ >= nwi) return;
+    {
+      const uint64_t itu = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(it_ >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)it_);
+      const uint64_t pf = itu * (HALF ? 32u : 64u);   // the iteration's first piece (it exists: it_ < nwi)
+      const uint64_t mf = __umul64hi(pf, blk_inv) + pf * one_piece_blocks;
+      // (the indices go through a vector register on purpose: from scalar ones these would be SCALAR loads, which share their counter
+      //  with the LDS operations — the walk's first wait for an LDS read would then wait for these trips to memory as well)
+      uint32_t vw, vm;
+      asm("v_mov_b32 %0, %1" : "=v"(vw) : "s"((uint32_t)(pf / DF_WBASE_PIECES)));
+      asm("v_mov_b32 %0, %1" : "=v"(vm) : "s"((uint32_t)mf));
+      o.wb = wbase[vw]; o.off0 = off[vm]; o.sp0 = spill[vm];
+    }
     const uint64_t u = it_ * 64 + lane;
     const bool ok = u < nunits;
     const uint64_t pc = HALF ? u >> 1 : u;
@@ -705,19 +793,11 @@ __global__ __launch_bounds__(WAVES * 64) void k_demit(const uint8_t* __restrict_
       }
     } else load_piece(in, n, ustart, o.w);
     // the four bytes before the unit (the copied bytes of its first K steps); the first unit's pending steps copy nothing, so it may
-    // read anything: an unconditional load from an address that is always valid (same reason as for r1 below)
+    // read anything.  Like the record's, an unconditional load from a clamped address that is always valid: a register that is written
+    // both by a load under a branch and by a plain move makes the compiler wait, right here, for loads that are still in flight (it
+    // cannot count the memory operations of the flush loop) — i.e. for this very prefetch
     o.wp = *reinterpret_cast<const uint32_t*>(ok && ustart >= 4 ? in + ustart - 4 : reinterpret_cast<const uint8_t*>(D.img));
-    const uint64_t pc0 = ok ? pc : 0;
-    const uint64_t m0 = __umul64hi(pc0, blk_inv) + pc0 * one_piece_blocks;
-    o.r = *reinterpret_cast<const uint4*>(rec + pc0);
-    o.off0 = off[m0]; o.sp0 = spill[m0];
-    // the piece behind this one (only lane 63's is used: where the wave's output ends).  Loaded by every lane, unconditionally: a
-    // register that is written both by a load under a branch and by a plain move makes the compiler wait, right here, for loads
-    // that are still in flight (it cannot count the memory operations of the flush loop) — i.e. for this very prefetch
-    {
-      const uint64_t pc1 = pc0 + 1 < npieces_total ? pc0 + 1 : pc0, m1 = __umul64hi(pc1, blk_inv) + pc1 * one_piece_blocks;
-      o.r1 = *reinterpret_cast<const uint4*>(rec + pc1); o.off1 = off[m1]; o.sp1 = spill[m1];
-    }
+    o.r = *reinterpret_cast<const uint2*>(rec + (ok ? pc : 0));
   };
   // `cur` = the operands of the iteration at work, `nx` = those of the next one, in flight since the top of this one.  `cur = nx` is
   // done BEFORE the iteration's flush: at that point the only memory operations in flight are the prefetch loads themselves, long
@@ -744,19 +824,18 @@ __global__ __launch_bounds__(WAVES * 64) void k_demit(const uint8_t* __restrict_
     uint32_t w[NW];
 #pragma unroll
     for (int i = 0; i < NW; ++i) w[i] = cur.w[i];
-    const uint32_t wp = cur.wp, lenA = cur.r.z & 0xFFFFu;
-    const uint32_t kA = HALF ? (half ? (cur.r.w >> 8) & 0xFFu : cur.r.w & 0xFFu) : cur.r.w & 0xFFu, kB = HALF ? 0u : (cur.r.w >> 8) & 0xFFu;
-    const uint32_t hh = HALF ? (half ? cur.r.x >> 16 : cur.r.x & 0xFFFFu) : cur.r.x;
-    uint64_t ostart = valid ? cur.off0 + cur.r.y + ((cur.r.z & DFREC_OWN) ? cur.sp0 : 0u) + (half ? lenA : 0u) : oend_all;
-    const uint64_t onext63 = piece + 1 < npieces_total ? cur.off1 + cur.r1.y + ((cur.r1.z & DFREC_OWN) ? cur.sp1 : 0u) : oend_all;
-    // end of the unit's output = start of the next unit's
-    uint64_t oend;
-    {
-      const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)ostart, 0x130, 0xF, 0xF, false);          // wave_shl:1
-      const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(ostart >> 32), 0x130, 0xF, 0xF, false);
-      oend = lane == 63 ? onext63 : ((uint64_t)hi << 32) | lo;
-      if (!valid) oend = oend_all;
-    }
+    const uint32_t wp = cur.wp;
+    const DfRec rc{cur.r.x, cur.r.y};
+    const bool hole = valid && dfrec_hole(rc);   // (a piece the forward pass resolved on the slow path: its lane replays the side entries)
+    const uint32_t len = hole ? dfrec_hole_len(rc) : dfrec_len(rc), lenA = hole ? len : dfrec_lenA(rc);   // (a hole's first half-unit replays the whole piece)
+    const uint32_t kA = HALF ? (half ? dfrec_kB(rc) : dfrec_kA(rc)) : dfrec_kA(rc), kB = HALF ? 0u : dfrec_kB(rc);
+    const uint32_t hA = HALF ? (half ? dfrec_middle(rc) : dfrec_start(rc)) : dfrec_start(rc), hB = dfrec_middle(rc);
+    // the output is contiguous: a unit's starts where the iteration's first unit's does (the wave's base) + what the units before it
+    // in the wave write; it ends its own length behind
+    const uint32_t ulen = valid ? (HALF ? (half ? len - lenA : lenA) : len) : 0u;
+    const uint32_t before = wave_scan_incl(ulen) - ulen;
+    const uint64_t obase = cur.off0 + (cur.wb & ~DFREC_OWN) + ((cur.wb & DFREC_OWN) ? cur.sp0 : 0u);
+    const uint64_t ostart = valid ? obase + before : oend_all, oend = valid ? ostart + ulen : oend_all;
     const unsigned long long vmask = __ballot(valid);
     const uint32_t nvalid = (uint32_t)__popcll(vmask);
     uint32_t first = 0;
@@ -766,11 +845,11 @@ __global__ __launch_bounds__(WAVES * 64) void k_demit(const uint8_t* __restrict_
     // pieces the forward pass resolved on its slow path: what their steps write is in the side entries (entry = copy | constant << 1,
     // bit 31: no input byte); their lanes replay them straight into the output, all of an iteration's at once (a stretch is a run of
     // neighbouring pieces: one after the other they cost a wave a millisecond)
-    if (valid && (cur.r.w & DFREC_HOLE) == DFREC_HOLE && half == 0) {
-      const uint32_t cntE = cur.r.w & 0x7FFFu;
-      uint64_t u = (cur.r.w & 0x8000u) ? piece * PIECE - K : piece * PIECE, o = ostart;   // (the first piece of a stretch also writes the K pending steps)
+    if (hole && half == 0) {
+      const uint32_t cntE = dfrec_hole_entries(rc), e0 = dfrec_hole_side(rc);
+      uint64_t u = dfrec_hole_first(rc) ? piece * PIECE - K : piece * PIECE, o = ostart;   // (the first piece of a stretch also writes the K pending steps)
       for (uint32_t x = 0; x < cntE; ++x) {
-        const uint32_t ee = side[cur.r.x + x], pc = (ee >> 1) & 0x3FFFFFFFu;
+        const uint32_t ee = side[e0 + x], pc = (ee >> 1) & 0x3FFFFFFFu;
         if (ee & 1u) out[o++] = in[u];
         if (pc < D.sl_npc) for (uint32_t b = D.sl_pcoff[pc]; b < D.sl_pcoff[pc + 1]; ++b) out[o++] = D.sl_pcpool[b];
         if (!(ee >> 31)) ++u;
@@ -783,7 +862,6 @@ __global__ __launch_bounds__(WAVES * 64) void k_demit(const uint8_t* __restrict_
       if (first == 0) request(it + (uint64_t)gridDim.x * WAVES, nx);
       const uint64_t gs = wave_read64(ostart, first);
       const uint64_t abase = gs & ~15ull;
-      const bool hole = (cur.r.w & DFREC_HOLE) == DFREC_HOLE;   // (a piece the forward pass resolved on the slow path: its lane replays the side entries)
       const bool fits = valid && lane >= first && (oend - abase) <= (uint64_t)stgb && plen == NB && !hole;
       const unsigned long long fm = __ballot(fits) >> first;
       uint32_t cnt = fm == ~0ull ? 64u - first : (uint32_t)__builtin_ctzll(~fm);
@@ -794,7 +872,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_demit(const uint8_t* __restrict_
           // (replayed in front of the rounds, with every other such piece of the iteration)
         } else
         if (lane == first) {
-          uint32_t h = hh & 0xFFFFu;
+          uint32_t h = hA;
           uint64_t o = ostart;
           for (int t = 0; t < plen; ++t) {
             const int ts = t - K;
@@ -823,16 +901,16 @@ __global__ __launch_bounds__(WAVES * 64) void k_demit(const uint8_t* __restrict_
         // HALF: the lane's one chain
         uint32_t oA = o0, pA = jarea + incl - need;
         if constexpr (HALF) {
-          if (D.wide) { if constexpr (K == 1) piece_dfwalk1cw_k1(w, wp, hh & 0xFFFFu, oA, pA); else piece_dfwalk1cw_k2(w, wp, hh & 0xFFFFu, oA, pA); }
-          else { if constexpr (K == 1) piece_dfwalk1c_k1(w, wp, hh & 0xFFFFu, oA, pA); else piece_dfwalk1c_k2(w, wp, hh & 0xFFFFu, oA, pA); }
+          if (D.wide) { if constexpr (K == 1) piece_dfwalk1cw_k1(w, wp, hA, oA, pA); else piece_dfwalk1cw_k2(w, wp, hA, oA, pA); }
+          else { if constexpr (K == 1) piece_dfwalk1c_k1(w, wp, hA, oA, pA); else piece_dfwalk1c_k2(w, wp, hA, oA, pA); }
         } else {
           uint32_t oB = o0 + lenA, pB = pA + 4u * kA;
           if (D.wide) {   // (more than 31 byte classes: one more shift per step)
-            if constexpr (K == 1) piece_dfwalk2cw_k1(w, wp, hh & 0xFFFFu, oA, hh >> 16, oB, pA, pB);
-            else piece_dfwalk2cw_k2(w, wp, hh & 0xFFFFu, oA, hh >> 16, oB, pA, pB);
+            if constexpr (K == 1) piece_dfwalk2cw_k1(w, wp, hA, oA, hB, oB, pA, pB);
+            else piece_dfwalk2cw_k2(w, wp, hA, oA, hB, oB, pA, pB);
           } else {
-            if constexpr (K == 1) piece_dfwalk2c_k1(w, wp, hh & 0xFFFFu, oA, hh >> 16, oB, pA, pB);
-            else piece_dfwalk2c_k2(w, wp, hh & 0xFFFFu, oA, hh >> 16, oB, pA, pB);
+            if constexpr (K == 1) piece_dfwalk2c_k1(w, wp, hA, oA, hB, oB, pA, pB);
+            else piece_dfwalk2c_k2(w, wp, hA, oA, hB, oB, pA, pB);
           }
         }
       }
@@ -842,7 +920,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_demit(const uint8_t* __restrict_
         if (!inplace && lane == first) atomicAdd(&flags->emit_ovf, cnt);
         if (active) {
           for (int ch = 0; ch < (HALF ? 1 : 2); ++ch) {
-            uint32_t h = ch ? hh >> 16 : hh & 0xFFFFu;
+            uint32_t h = ch ? hB : hA;
             uint64_t o = (uint64_t)(o0 - stga) + (ch ? lenA : 0u);
             for (int t = ch * HALF_BYTES; t < (ch + 1) * HALF_BYTES; ++t) {
               const int ts = t - K;
