@@ -37,6 +37,12 @@ for seed in range(int(os.environ.get("SOAK_LO", 300)), int(os.environ.get("SOAK_
     cands = []
     for k in (50, 400, 3000):
         cands.append(b"".join(rng.choice(pool) for _ in range(k)))
+    if os.environ.get("SOAK_SAMPLED"):   # also inputs walked off the program's own transducer (randprog.accepted_input), with their variants
+        from kleenexlang_amd import host
+        fst = host.dump_fst(src)[0]
+        for k in (4097, 20500):
+            data = randprog.accepted_input(fst, rng, k)
+            cands += [data] + randprog.rejected_variants(data, rng)
     for seg in (64, 1024, 4096):
         try:
             p = Program(blob, segment_bytes=seg)

@@ -49,6 +49,20 @@ def test_random_programs_three_routes_agree():
     assert checked > 1000 and accepted > 100, (checked, accepted)
 
 
+def assert_first_dead_prefix(fst, data, pos, where):
+    """`pos` is the length of the longest prefix of `data` that still has a live path through the transducer (the paths' outputs are
+    dropped on the way: only which states are alive counts, and positions far inside a long input stay cheap)"""
+    # a live path exists for data[:pos] (the run got that far) …
+    paths = fst_sim._close(fst, [(b"", fst["init"])])
+    for b in data[:pos]:
+        paths = fst_sim._close(fst, [(b"", t) for a, q in paths for rg, cp, t, *_ in fst["sym"][q] if any(lo <= b <= hi for lo, hi in rg)])
+    assert paths, (where, data[:80], pos)
+    if pos < len(data):   # … and none survives the next symbol
+        b = data[pos]
+        nxt = [(b"", t) for a, q in paths for rg, cp, t, *_ in fst["sym"][q] if any(lo <= b <= hi for lo, hi in rg)]
+        assert not fst_sim._close(fst, nxt), (where, data[:80], pos)
+
+
 def test_random_programs_failure_position_is_first_dead_prefix():
     """count in "Match error at input symbol <count>" = length of the longest prefix that still has a live path."""
     for seed in range(0, NPROG, 3):
@@ -63,15 +77,7 @@ def test_random_programs_failure_position_is_first_dead_prefix():
                 continue
             except oracle.OracleMatchError as e:
                 pos = e.pos
-            # a live path exists for data[:pos] (the run got that far) …
-            paths = fst_sim._close(fst, [(b"", fst["init"])])
-            for b in data[:pos]:
-                paths = fst_sim._close(fst, [(a, t) for a, q in paths for rg, cp, t, *_ in fst["sym"][q] if any(lo <= b <= hi for lo, hi in rg)])
-            assert paths, (seed, data, pos)
-            if pos < len(data):   # … and none survives the next symbol
-                b = data[pos]
-                nxt = [(a, t) for a, q in paths for rg, cp, t, *_ in fst["sym"][q] if any(lo <= b <= hi for lo, hi in rg)]
-                assert not fst_sim._close(fst, nxt), (seed, data, pos)
+            assert_first_dead_prefix(fst, data, pos, seed)
 
 
 @pytest.mark.gpu
