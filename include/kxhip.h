@@ -455,6 +455,36 @@ int kx_run_batch_field_list(kx_program* prog, const void* d_in, const uint64_t* 
 int kx_run_records_fd_field_list(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_field_range* ranges,
                                  uint32_t n_ranges, uint8_t fs, int report_fd, kx_records_stats* stats);
 
+/* ---- field mode on unquoted values: the program runs on the VALUE of every selected field, the field is re-spelled -----------------
+ * kx_run_batch_field_values is kx_run_batch_field_list in everything not said here: the records, the live `fs` bytes, the list, `need`,
+ * "all selected fields accepted or nothing", return codes, KX_E_CAPACITY and the size query, d_docs, d_fail_field and the statistics.
+ *   The program runs on the VALUE of a selected field (host.unquote_field_model): the field's bytes without the quote bytes that
+ *     open and close quoted stretches and without the escape bytes; a quote that opens right behind one that closed (the "" of a
+ *     quoted field) is one quote byte of the value; the byte behind an unescaped escape byte is data, a last escape byte alone is
+ *     dropped.  The rule is total: a quote in the middle of a field toggles the state, an unclosed one is simply dropped.  fail_pos
+ *     counts inside the value.
+ *   An accepted record's selected fields are replaced by the SPELLING of the program's outputs (host.requote_field_model).  `special`
+ *     are the bytes that must not appear bare (the records driver passes the record separator); was_quoted: the list has a quote byte
+ *     and the raw field begins with it.  Quote, no escape: the output is wrapped iff was_quoted or it holds fs, the quote or a special
+ *     byte — the quote byte, the output with every quote byte doubled, the quote byte; else it goes out as it is.  Escape: every
+ *     escape byte gets an escape byte in front of it; with a quote every quote byte too, and the result is wrapped in quote bytes iff
+ *     was_quoted or the output holds fs or a special byte; without a quote every fs and every special byte gets one as well.  An
+ *     accepted empty output of a quoted field is two quote bytes.
+ * KX_E_ARG besides kx_run_batch_field_list's, before any device work: a null codec or a wrong `size`, n_special > 8, a non-zero
+ * reserved word, a special byte equal to the quote or the escape byte, a list with quote = escape = -1.  Per call the library holds,
+ * beside kx_run_batch_field_list's workspace, 17 bytes per selected field, the values' bytes and the spellings' bytes. */
+typedef struct kx_field_codec { uint32_t size; uint32_t n_special; uint8_t special[8]; uint32_t reserved[4]; } kx_field_codec;
+int kx_run_batch_field_values(kx_program* prog, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* list,
+                              const kx_field_codec* codec, void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs,
+                              uint32_t* d_fail_field, size_t* out_len, kx_batch_stats* stats, void* stream);
+
+/* kx_run_records_fd_field_list on values (`BIN --records … --quote|--escape --field=K|LIST [--fs=F] --unquote`): every record goes
+ * through kx_run_batch_field_values with special = {o->sep}.  A rejected field always reports "Match error at input symbol S in field
+ * K of record R!", S counted inside the value.  KX_E_ARG: kx_run_records_fd_field_list's, and a mode other than KX_RECORDS_QUOTED and
+ * KX_RECORDS_ESCAPED. */
+int kx_run_records_fd_field_values(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_field_range* ranges,
+                                   uint32_t n_ranges, uint8_t fs, int report_fd, kx_records_stats* stats);
+
 /* ---- sharded execution: one contiguous shard of the input per GPU -------------
  * Per stage and per rank:
  *   kx_shard_begin → kx_shard_forward → [exchange kx_fwd_summary] → kx_shard_fix_head

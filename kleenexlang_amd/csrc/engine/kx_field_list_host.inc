@@ -6,6 +6,8 @@
 // entries) → k_flsplen → scan of the output lengths into the caller's offsets → k_flsplice.  Host round trips of its own: the
 // offset check, the documents' total, the fields' total, the output's total.  With no document (every record too short) the steps
 // from k_fllocate to kx_run_batch are skipped.  HIP-event times add into kx_fields_stats's groups (count and locate: locate_ms).
+// The driver, runFieldList, is also kx_run_batch_field_values's (kx_field_values_host.inc): with a codec the program runs on the
+// fields' values, and their spellings are spliced.
 
 #include "kx_field_list.h"
 
@@ -26,14 +28,14 @@ int checkFieldList(const kx_batch_field_list& l, const char* who) {
   return checkFields(f, who);
 }
 
-}  // namespace
-
-extern "C" int kx_run_batch_field_list(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* l,
-                                       void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs, uint32_t* d_fail_field, size_t* out_len,
-                                       kx_batch_stats* stats, void* stream) {
-  static const char* const who = "kx_run_batch_field_list";
-  if (!p || !out_len || !l) return setErr(KX_E_ARG, "null argument");
-  if (const int rc = checkFieldList(*l, who)) return rc;
+// The driver of kx_run_batch_field_list (codec = null) and of kx_run_batch_field_values (kx_field_values_host.inc; `who` names the
+// entry point, whose checks of `l` and `codec` have passed).  With a codec the documents the program runs on are the fields' VALUES
+// — k_fvdeclen, a scan and k_fvdecode take k_fgather's place — and k_fvenclen, a scan and k_fvencode spell the program's outputs
+// before k_flsplen and k_flsplice, which then take the spellings and their offsets for the outputs and theirs (kx_field_values.inc).
+// Without one, the kernels and their arguments are the list's own.
+int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* l,
+                 const kx_field_codec* codec, void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs, uint32_t* d_fail_field,
+                 size_t* out_len, kx_batch_stats* stats, void* stream, const char* who) {
   if (n_docs && (!d_in_off || !d_out_off || !d_docs)) return setErr(KX_E_ARG, std::string(who) + ": offsets, output offsets and document records are required");
   if (n_docs >= 0xFFFFFFFFull) return setErr(KX_E_ARG, std::string(who) + ": at most 2^32 - 2 documents per call");
   *out_len = 0;
@@ -45,11 +47,17 @@ extern "C" int kx_run_batch_field_list(kx_program* p, const void* d_in, const ui
   }
   if (!p->field_list) p->field_list = new FieldListWs;
   if (!p->fields) p->fields = new FieldWs;   // (its times are kx_fields_stats's)
+  if (codec && !p->field_values) p->field_values = new FieldValuesWs;
   FieldListWs& W = *p->field_list;
+  FieldValuesWs* const V = codec ? p->field_values : nullptr;
   const bool timing = p->cfg.collect_timing != 0;
   if (timing && !W.have_events) {
     for (auto& e : W.ev) HIPCHECK(hipEventCreate(&e));
     W.have_events = true;
+  }
+  if (timing && V && !V->have_events) {
+    for (auto& e : V->ev) HIPCHECK(hipEventCreate(&e));
+    V->have_events = true;
   }
   const uint64_t nd = n_docs;
   int rc = BatchWs::ensure(W.ctr, FC_N * 8);
@@ -123,6 +131,7 @@ extern "C" int kx_run_batch_field_list(kx_program* p, const void* d_in, const ui
   kx_batch_stats bst{};
   unsigned long long *fb = nullptr, *fe = nullptr, *coff = nullptr, *poff = nullptr;
   kx_batch_doc* drec = nullptr;
+  const uint8_t* spliced = nullptr;   // with a codec: the spellings, which k_flsplice takes for the program's outputs
   if (ndocs) {
     // 2. the documents' bounds, and the scan of their lengths
     for (BatchWs::Buf* b : {&W.fb, &W.fe}) if (!rc) rc = BatchWs::ensure(*b, ndocs * 8);
@@ -134,6 +143,13 @@ extern "C" int kx_run_batch_field_list(kx_program* p, const void* d_in, const ui
     fb = (unsigned long long*)W.fb.p; fe = (unsigned long long*)W.fe.p; coff = (unsigned long long*)W.coff.p; poff = (unsigned long long*)W.poff.p;
     drec = (kx_batch_doc*)W.drec.p;
     BDoc* len = (BDoc*)W.len.p;
+    FVSpec C{};           // with a codec only: the bytes of the value kernels, and their grid (lane = document)
+    uint32_t dgrid = 0;
+    if (V) {
+      C = FVSpec{l->fs, L.F.quote, L.F.escape, codec->n_special, 0ull};
+      for (uint32_t i = 0; i < C.nsp; ++i) C.sp8 |= (unsigned long long)codec->special[i] << (8 * i);
+      dgrid = (uint32_t)std::min<uint64_t>((ndocs + FLD_BT - 1) / FLD_BT, (uint64_t)p->ncu * 4);
+    }
     if (timing) HIPCHECK(hipEventRecord(W.ev[3], sm));
     auto* const locate = mode == FLD_ESCAPED ? &k_fllocate<FLD_ESCAPED> : mode == FLD_QUOTED ? &k_fllocate<FLD_QUOTED> : &k_fllocate<FLD_PLAIN>;
     hipLaunchKernelGGL(locate, dim3(bgrid), dim3(FLD_BT), 0, sm, in, off, (unsigned long long)nd, L, (const unsigned long long*)d0, fb, fe, len);
@@ -144,25 +160,72 @@ extern "C" int kx_run_batch_field_list(kx_program* p, const void* d_in, const ui
     unsigned long long ctotal = 0;
     HIPCHECK(hipMemcpyAsync(&ctotal, &fl->total_len, 8, hipMemcpyDeviceToHost, sm));
     HIPCHECK(hipStreamSynchronize(sm));
-    // 3. the compact buffer
-    rc = BatchWs::ensure(W.comp, ctotal + 32);
-    if (rc) return rc;
-    if (timing) HIPCHECK(hipEventRecord(W.ev[6], sm));
-    hipLaunchKernelGGL(k_fgather, granGrid(ctotal), dim3(FLD_GT), 0, sm, in, (const unsigned long long*)fb, (const unsigned long long*)coff,
-                       ndocs, ctotal, (uint8_t*)W.comp.p);
-    if (timing) HIPCHECK(hipEventRecord(W.ev[7], sm));
-    HIPCHECK(hipGetLastError());
+    // 3. the compact buffer: the fields' bytes, or their values
+    const void* docs_in = nullptr;                // what the program runs on: ndocs documents at docs_off, docs_total bytes
+    const unsigned long long* docs_off = coff;
+    unsigned long long docs_total = ctotal;
+    if (!V) {
+      rc = BatchWs::ensure(W.comp, ctotal + 32);
+      if (rc) return rc;
+      if (timing) HIPCHECK(hipEventRecord(W.ev[6], sm));
+      hipLaunchKernelGGL(k_fgather, granGrid(ctotal), dim3(FLD_GT), 0, sm, in, (const unsigned long long*)fb, (const unsigned long long*)coff,
+                         ndocs, ctotal, (uint8_t*)W.comp.p);
+      if (timing) HIPCHECK(hipEventRecord(W.ev[7], sm));
+      HIPCHECK(hipGetLastError());
+      docs_in = W.comp.p;
+    } else {
+      for (BatchWs::Buf* b : {&V->uoff, &V->qoff}) if (!rc) rc = BatchWs::ensure(*b, (ndocs + 1) * 8);
+      if (!rc) rc = BatchWs::ensure(V->vflag, ndocs);
+      if (rc) return rc;
+      unsigned long long* uoff = (unsigned long long*)V->uoff.p;
+      if (timing) HIPCHECK(hipEventRecord(V->ev[0], sm));
+      auto* const declen = mode == FLD_ESCAPED ? &k_fvdeclen<FLD_ESCAPED> : &k_fvdeclen<FLD_QUOTED>;
+      hipLaunchKernelGGL(declen, dim3(dgrid), dim3(FLD_BT), 0, sm, in, (const unsigned long long*)fb, (const unsigned long long*)fe, ndocs, C, len,
+                         (uint8_t*)V->vflag.p);   // (the fields' lengths have been scanned into coff)
+      scanLens(len, ndocs, uoff);
+      HIPCHECK(hipGetLastError());
+      HIPCHECK(hipMemcpyAsync(&docs_total, &fl->total_len, 8, hipMemcpyDeviceToHost, sm));
+      HIPCHECK(hipStreamSynchronize(sm));
+      rc = BatchWs::ensure(V->ucomp, docs_total + 32);
+      if (rc) return rc;
+      auto* const decode = mode == FLD_ESCAPED ? &k_fvdecode<FLD_ESCAPED> : &k_fvdecode<FLD_QUOTED>;
+      hipLaunchKernelGGL(decode, dim3(dgrid), dim3(FLD_BT), 0, sm, in, (const unsigned long long*)fb, (const unsigned long long*)fe, ndocs, C,
+                         (const unsigned long long*)uoff, (uint8_t*)V->ucomp.p);
+      if (timing) HIPCHECK(hipEventRecord(V->ev[1], sm));
+      HIPCHECK(hipGetLastError());
+      docs_in = V->ucomp.p; docs_off = uoff;
+    }
     // 4. the program on every selected field
     size_t pl = 0;
-    rc = BatchWs::ensure(W.pout, ctotal + ctotal / 2 + 4096);
+    const size_t slack = V ? 16 : 0;              // (k_fvenclen and k_fvencode read the outputs' last granule whole)
+    rc = BatchWs::ensure(W.pout, docs_total + docs_total / 2 + 4096 + slack);
     if (rc) return rc;
-    rc = kx_run_batch(p, W.comp.p, (const uint64_t*)coff, ndocs, W.pout.p, W.pout.cap, (uint64_t*)poff, drec, &pl, &bst, stream);
+    rc = kx_run_batch(p, docs_in, (const uint64_t*)docs_off, ndocs, W.pout.p, W.pout.cap - slack, (uint64_t*)poff, drec, &pl, &bst, stream);
     if (rc == KX_E_CAPACITY) {
-      rc = BatchWs::ensure(W.pout, pl + 16);
+      rc = BatchWs::ensure(W.pout, pl + 16 + slack);
       if (rc) return rc;
-      rc = kx_run_batch(p, W.comp.p, (const uint64_t*)coff, ndocs, W.pout.p, W.pout.cap, (uint64_t*)poff, drec, &pl, &bst, stream);
+      rc = kx_run_batch(p, docs_in, (const uint64_t*)docs_off, ndocs, W.pout.p, W.pout.cap - slack, (uint64_t*)poff, drec, &pl, &bst, stream);
     }
     if (rc != 0 && rc != KX_MATCH_ERROR) return rc;
+    // 4v. the spellings of the outputs take the outputs' place
+    if (V) {
+      unsigned long long* qoff = (unsigned long long*)V->qoff.p;
+      if (timing) HIPCHECK(hipEventRecord(V->ev[2], sm));
+      hipLaunchKernelGGL(k_fvenclen, dim3(dgrid), dim3(FLD_BT), 0, sm, (const uint8_t*)W.pout.p, (const unsigned long long*)poff, (const kx_batch_doc*)drec,
+                         ndocs, C, (uint8_t*)V->vflag.p, len);
+      scanLens(len, ndocs, qoff);
+      HIPCHECK(hipGetLastError());
+      unsigned long long qtotal = 0;
+      HIPCHECK(hipMemcpyAsync(&qtotal, &fl->total_len, 8, hipMemcpyDeviceToHost, sm));
+      HIPCHECK(hipStreamSynchronize(sm));
+      rc = BatchWs::ensure(V->qout, qtotal + 16);
+      if (rc) return rc;
+      hipLaunchKernelGGL(k_fvencode, dim3(dgrid), dim3(FLD_BT), 0, sm, (const uint8_t*)W.pout.p, (const unsigned long long*)poff, (const kx_batch_doc*)drec,
+                         ndocs, C, (const uint8_t*)V->vflag.p, (const unsigned long long*)qoff, (uint8_t*)V->qout.p);
+      if (timing) HIPCHECK(hipEventRecord(V->ev[3], sm));
+      HIPCHECK(hipGetLastError());
+      poff = qoff; spliced = (const uint8_t*)V->qout.p;
+    }
   }
   // 5. the records' results and output lengths, and their scan into the caller's offsets
   BDoc* rlen = cnt;   // (the counts have been scanned into d0)
@@ -188,8 +251,8 @@ extern "C" int kx_run_batch_field_list(kx_program* p, const void* d_in, const ui
   if (timing) HIPCHECK(hipEventRecord(W.ev[10], sm));
   if (total)
     hipLaunchKernelGGL(k_flsplice, granGrid(total), dim3(FLD_GT), 0, sm, in, off, (unsigned long long)nd, L.F, (const unsigned long long*)d0,
-                       (const unsigned long long*)fb, (const unsigned long long*)fe, (const unsigned long long*)coff, (const uint8_t*)W.pout.p,
-                       (const unsigned long long*)poff, (const unsigned long long*)d_out_off, total, sfx8, (uint8_t*)d_out);
+                       (const unsigned long long*)fb, (const unsigned long long*)fe, (const unsigned long long*)coff,
+                       spliced ? spliced : (const uint8_t*)W.pout.p, (const unsigned long long*)poff, (const unsigned long long*)d_out_off, total, sfx8, (uint8_t*)d_out);
   if (timing) HIPCHECK(hipEventRecord(W.ev[11], sm));
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipStreamSynchronize(sm));
@@ -197,9 +260,24 @@ extern "C" int kx_run_batch_field_list(kx_program* p, const void* d_in, const ui
     FieldWs& T = *p->fields;
     T.locate_ms += evMs(W.ev[0], W.ev[1]) + (ndocs ? evMs(W.ev[3], W.ev[4]) : 0.f);
     T.scan_ms += evMs(W.ev[1], W.ev[2]) + (ndocs ? evMs(W.ev[4], W.ev[5]) : 0.f) + evMs(W.ev[8], W.ev[9]);   // (the last with k_flsplen, which feeds it)
-    T.gather_ms += ndocs ? evMs(W.ev[6], W.ev[7]) : 0.f;
+    T.gather_ms += ndocs && !V ? evMs(W.ev[6], W.ev[7]) : 0.f;   // (with a codec nothing is gathered: the two events are not recorded)
     T.splice_ms += evMs(W.ev[10], W.ev[11]);
+    if (V && ndocs) {   // (the values' decoding counts with the gather it replaces, the outputs' spelling with the splice it feeds)
+      T.gather_ms += evMs(V->ev[0], V->ev[1]);
+      T.splice_ms += evMs(V->ev[2], V->ev[3]);
+    }
     ++T.calls;
   }
   return rej ? KX_MATCH_ERROR : 0;
+}
+
+}  // namespace
+
+extern "C" int kx_run_batch_field_list(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* l,
+                                       void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs, uint32_t* d_fail_field, size_t* out_len,
+                                       kx_batch_stats* stats, void* stream) {
+  static const char* const who = "kx_run_batch_field_list";
+  if (!p || !out_len || !l) return setErr(KX_E_ARG, "null argument");
+  if (const int rc = checkFieldList(*l, who)) return rc;
+  return runFieldList(p, d_in, d_in_off, n_docs, l, nullptr, d_out, cap, d_out_off, d_docs, d_fail_field, out_len, stats, stream, who);
 }

@@ -24,7 +24,9 @@
 // Field mode (kx_run_records_fd_fields): RecordsRun::batch calls kx_run_batch_fields (kx_fields_host.inc) instead — the carried
 // record and the window's records alike — with the split's quote and escape byte, the separator's length and, unless `chomp`, the
 // separator kept behind the record's output.  A record without the field is reported in a line of its own kind.  With a list of
-// fields (kx_run_records_fd_field_list) it calls kx_run_batch_field_list the same way; the report lines name the field.
+// fields (kx_run_records_fd_field_list) it calls kx_run_batch_field_list the same way; the report lines name the field.  On unquoted
+// values (kx_run_records_fd_field_values) it calls kx_run_batch_field_values with the list and a codec whose one special byte is the
+// record separator.
 
 namespace {
 
@@ -239,6 +241,7 @@ struct RecordsRun {
   uint8_t fsep = 0;                                    //   ... of the fields that `fsep` separates
   kx_field_range ranges[8] = {};                       // field mode with a list: the program runs on the fields of ranges[0, n_ranges)
   uint32_t n_ranges = 0;                               //   (0: no list; `field` is 0 with a list)
+  kx_field_codec codec{};                              // ... on their values (size != 0: kx_run_batch_field_values; special = the separator)
   SplitCarry next;                                     // what the next window's split starts from
   int report_fd = -1;
   RecWs ws;
@@ -301,6 +304,9 @@ struct RecordsRun {
     ll.suffix_len = fl.suffix_len;
     memcpy(ll.suffix, fl.suffix, sizeof ll.suffix);
     auto run = [&](void* d_out, size_t cap, size_t* ol, kx_batch_stats* bs) {
+      if (n_ranges && codec.size)
+        return kx_run_batch_field_values(p, in, d_o, ndocs, &ll, &codec, d_out, cap, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, (uint32_t*)ffield.p, ol,
+                                         bs, nullptr);
       if (n_ranges)
         return kx_run_batch_field_list(p, in, d_o, ndocs, &ll, d_out, cap, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, (uint32_t*)ffield.p, ol, bs,
                                        nullptr);
@@ -539,7 +545,7 @@ int checkRecordsOpts(const kx_records_opts& o, const char* who, int fs = -1) {
 
 // the stream on in_fd in record mode as `o` says (checkRecordsOpts has passed)
 int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o, int report_fd, kx_records_stats* stats, uint32_t field = 0,
-                 uint8_t fsep = 0, const kx_field_range* ranges = nullptr, uint32_t n_ranges = 0) {
+                 uint8_t fsep = 0, const kx_field_range* ranges = nullptr, uint32_t n_ranges = 0, bool values = false) {
   if (!p) return setErr(KX_E_ARG, "null argument");
   if (p->cfg.phase) return setErr(KX_E_ARG, "record mode runs every phase: kx_config::phase must be 0");
   const double t_begin = FdStream::nowMs();
@@ -555,6 +561,7 @@ int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o,
   R.p = p; R.fs = &fsr; R.o = o; R.report_fd = report_fd; R.field = field; R.fsep = fsep;
   R.n_ranges = n_ranges;
   if (n_ranges) memcpy(R.ranges, ranges, n_ranges * sizeof(kx_field_range));
+  if (values) { R.codec.size = sizeof R.codec; R.codec.n_special = 1; R.codec.special[0] = o.sep; }
   R.timing = p->cfg.collect_timing != 0;
   int rc = 0;
   if (R.timing) for (auto& e : R.ev) if (hipEventCreate(&e) != hipSuccess) rc = setErr(KX_E_HIP, "hipEventCreate failed");
@@ -621,4 +628,15 @@ extern "C" int kx_run_records_fd_field_list(kx_program* p, int in_fd, int out_fd
     return setErr(KX_E_ARG, "kx_run_records_fd_field_list: the field list is not in normal form (1 to 8 ranges: sorted, disjoint, not adjacent, only the last open)");
   if (const int rc = checkRecordsOpts(*o, "kx_run_records_fd_field_list", fs)) return rc;
   return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, 0, fs, ranges, n_ranges);
+}
+
+extern "C" int kx_run_records_fd_field_values(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_field_range* ranges,
+                                              uint32_t n_ranges, uint8_t fs, int report_fd, kx_records_stats* stats) {
+  static const char* const who = "kx_run_records_fd_field_values";
+  if (!o || !ranges) return setErr(KX_E_ARG, "null argument");
+  if (!kxFieldListIsNormal(ranges, n_ranges))
+    return setErr(KX_E_ARG, std::string(who) + ": the field list is not in normal form (1 to 8 ranges: sorted, disjoint, not adjacent, only the last open)");
+  if (const int rc = checkRecordsOpts(*o, who, fs)) return rc;
+  if (o->mode != KX_RECORDS_QUOTED && o->mode != KX_RECORDS_ESCAPED) return setErr(KX_E_ARG, std::string(who) + ": values need a quote or an escape byte");
+  return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, 0, fs, ranges, n_ranges, true);
 }

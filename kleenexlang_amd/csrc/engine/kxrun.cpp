@@ -21,8 +21,10 @@
 // escape rules leave live — and the rest of the record is copied around its output (kx_run_records_fd_fields); a record with
 // fewer fields writes nothing and is reported as "Record R has no field K!".  With `--field=LIST` (2,5-7,9-: anything but one
 // plain number) the program runs on every field of the list, each a whole input of its own, and the record is written only if all
-// of them are accepted (kx_run_records_fd_field_list; the list's parser is kx_field_list.h).  What --field and --fs refuse exits
-// with status 2.
+// of them are accepted (kx_run_records_fd_field_list; the list's parser is kx_field_list.h).  With `--unquote` (with --field, and
+// --quote or --escape) the program runs on the VALUE of each selected field, and the field is replaced by the spelling of its
+// output, quoted and escaped as it needs (kx_run_records_fd_field_values; --field=K is then the list K-K).  What --field, --fs and
+// --unquote refuse exits with status 2.
 //
 // BIN = this executable ++ KXP blob ++ libdir ++ trailer (see kexc main.cpp).
 // The engine is loaded with dlopen so that this file carries no HIP dependency.
@@ -88,6 +90,7 @@ static void usage(const char* name) {
   fprintf(stdout, "- \"%s --records ... --ors=STR\": the 0 to 8 bytes STR spells follow the output of every accepted record.\n", name);
   fprintf(stdout, "- \"%s --records ... --field=K [--fs=F]\": runs field K (from 1; fields end at F, default a tab) of every record, the rest is copied.\n", name);
   fprintf(stdout, "- \"%s --records ... --field=LIST [--fs=F]\": the same on every field of LIST (2,5-7,9-); a record is written only if all of them are accepted.\n", name);
+  fprintf(stdout, "- \"%s --records ... --quote|--escape --field=K|LIST [--fs=F] --unquote\": the program runs on the unquoted value of every selected field; its output is quoted again as it needs.\n", name);
 }
 
 // --records=SEP, --quote=Q, --escape=E: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
@@ -172,11 +175,12 @@ int main(int argc, char** argv) {
                                          {"records", optional_argument, 0, 'r'}, {"quote", optional_argument, 0, 'q'},
                                          {"escape", optional_argument, 0, 'e'}, {"rs", required_argument, 0, 's'},
                                          {"chomp", no_argument, 0, 'c'}, {"ors", required_argument, 0, 'o'},
-                                         {"field", required_argument, 0, 'f'}, {"fs", required_argument, 0, 'F'}, {0, 0, 0, 0}};
+                                         {"field", required_argument, 0, 'f'}, {"fs", required_argument, 0, 'F'},
+                                         {"unquote", no_argument, 0, 'u'}, {0, 0, 0, 0}};
   bool timing = false, records = false, quoted = false, escaped = false, sep_given = false, multi = false, chomp = false, ors_given = false;
   uint8_t sep = '\n', quote = '"', escape = '\\', rs[8] = {}, ors[8] = {};
   uint32_t rs_len = 0, ors_len = 0, field = 0;
-  bool field_given = false, fs_given = false;
+  bool field_given = false, fs_given = false, unquote = false;
   kx_field_range ranges[KX_FIELD_RANGES] = {};   // --field=LIST in normal form (n_ranges = 0: --field=K, one plain number)
   uint32_t n_ranges = 0;
   uint8_t fsep = '\t';
@@ -237,6 +241,7 @@ int main(int argc, char** argv) {
         fs_given = true;
         if (!parseSeparator(optarg, &fsep)) { fprintf(stderr, "Invalid --fs: %s (one byte)\n", optarg); return 2; }
         break;
+      case 'u': unquote = true; break;
       case 'h':
       default: usage(argv[0]); return 1;
     }
@@ -259,6 +264,9 @@ int main(int argc, char** argv) {
   if (field_given && (multi ? rs_len == 1 && fsep == rs[0] : fsep == sep)) { fprintf(stderr, "%s: --fs cannot be the record separator\n", argv[0]); return 2; }
   if (field_given && quoted && fsep == quote) { fprintf(stderr, "%s: --fs cannot be the --quote character\n", argv[0]); return 2; }
   if (field_given && escaped && fsep == escape) { fprintf(stderr, "%s: --fs cannot be the --escape character\n", argv[0]); return 2; }
+  if (unquote && !field_given) { fprintf(stderr, "%s: --unquote needs --field\n", argv[0]); return 2; }
+  if (unquote && !quoted && !escaped) { fprintf(stderr, "%s: --unquote needs --quote or --escape\n", argv[0]); return 2; }
+  if (unquote && !n_ranges) { ranges[0] = kx_field_range{field, field}; n_ranges = 1; }   // --field=K on values: the list K-K
   struct timeval t0, t1;
   if (timing) gettimeofday(&t0, nullptr);
 
@@ -287,7 +295,8 @@ int main(int argc, char** argv) {
     if (escaped && !(rune = (decltype(rune))engineSymbol(h, argv[0], "kx_run_records_fd_escaped", "--escape needs"))) return 1;
     if (multi && !(runm = (decltype(runm))engineSymbol(h, argv[0], "kx_run_records_fd_rs", "--rs needs"))) return 1;
     if (field_given && !n_ranges && !(runf = (decltype(runf))engineSymbol(h, argv[0], "kx_run_records_fd_fields", "--field needs"))) return 1;
-    if (n_ranges && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_list", "--field=LIST needs"))) return 1;
+    if (n_ranges && !unquote && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_list", "--field=LIST needs"))) return 1;
+    if (unquote && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_values", "--unquote needs"))) return 1;   // (the same signature)
     if (framing && !(runo = (decltype(runo))engineSymbol(h, argv[0], "kx_run_records_fd_opts", "--chomp and --ors need"))) return 1;
     // record mode is where the single-document route is unusable (a third of a millisecond per record): stages with register
     // actions are replayed by the batch kernels unless KX_BATCH_ACTIONS=0 asks for the route

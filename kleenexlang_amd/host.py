@@ -668,6 +668,90 @@ def field_list_records_model(data, offsets, sep_len, last_whole, ranges, fs, quo
     return res
 
 
+class KxFieldCodec(ctypes.Structure):
+    """include/kxhip.h::kx_field_codec."""
+    _fields_ = [("size", ctypes.c_uint32), ("n_special", ctypes.c_uint32), ("special", ctypes.c_uint8 * 8), ("reserved", ctypes.c_uint32 * 4)]
+
+
+def _check_codec(what, quote, escape, special=b""):
+    """The bytes of the two value models and of `unquote=`: a quote or an escape byte (or both, different), and 0 to 8 special
+    bytes that are neither → (Q, E, special) with None for a byte that is not set."""
+    if quote is None and escape is None:
+        raise ValueError("%s: values need a quote= or an escape= byte" % what)
+    q = None if quote is None else _one_byte(quote, "quote character")
+    e = None if escape is None else _one_byte(escape, "escape character")
+    if q is not None and q == e:
+        raise ValueError("escape character: %r is also the quote character" % bytes([e]))
+    if not isinstance(special, (bytes, bytearray)):
+        raise TypeError("%s: special must be bytes of length 0 to 8, not %s" % (what, type(special).__name__))
+    if len(special) > 8:
+        raise ValueError("%s: special must be 0 to 8 bytes, not %d" % (what, len(special)))
+    if any(b in (q, e) for b in special):
+        raise ValueError("%s: a special byte cannot be the quote or the escape character" % what)
+    return q, e, bytes(special)
+
+
+def unquote_field_model(raw, quote=None, escape=None):
+    """The VALUE of a field spelled `raw` — the normative model of `--unquote`'s decoding (kx_run_batch_field_values).  The quote
+    bytes that open and close quoted stretches and the escape bytes are not part of it: the byte behind an unescaped escape byte is
+    data (a last escape byte alone is dropped), a quote that opens right behind one that closed — the "" of a quoted field — is one
+    quote byte.  The rule is total and keeps the parity rule of the splitters: a quote in the middle of a field toggles the state,
+    an unclosed quote is simply dropped."""
+    if not isinstance(raw, (bytes, bytearray, memoryview)):
+        raise TypeError("unquote_field_model: raw must be bytes, not %s" % type(raw).__name__)
+    Q, E, _ = _check_codec("unquote_field_model", quote, escape)
+    raw = bytes(raw)
+    out, s, pc, i = bytearray(), 0, False, 0                    # s: inside quotes; pc: the previous byte was a closing quote
+    while i < len(raw):
+        b = raw[i]
+        if E is not None and b == E:
+            if i + 1 < len(raw):
+                out.append(raw[i + 1])
+            i += 2
+            pc = False
+            continue
+        if Q is not None and b == Q:
+            if s:
+                s, pc = 0, True
+            else:
+                s = 1
+                if pc:
+                    out.append(Q)
+                pc = False
+            i += 1
+            continue
+        out.append(b)
+        pc = False
+        i += 1
+    return bytes(out)
+
+
+def requote_field_model(value, was_quoted, fs, quote=None, escape=None, special=b"\n"):
+    """The SPELLING of a program output `value` in place of a field — the normative model of `--unquote`'s encoding.  `special`:
+    the bytes that must not appear bare (the records driver passes the record separator); `was_quoted`: a quote byte is set and
+    the raw field began with it.  Quote, no escape: wrapped — quote, the value with every quote doubled, quote — iff was_quoted or
+    the value holds `fs`, the quote or a special byte.  Escape: every escape byte gets an escape byte in front of it; with a quote
+    every quote byte too, and the result is wrapped iff was_quoted or the value holds `fs` or a special byte; without one every `fs`
+    and special byte gets one as well.  (A rejected field is spelled as nothing: that is the caller's, not this function's.)"""
+    if not isinstance(value, (bytes, bytearray, memoryview)):
+        raise TypeError("requote_field_model: value must be bytes, not %s" % type(value).__name__)
+    if not isinstance(was_quoted, bool):
+        raise TypeError("requote_field_model: was_quoted must be True or False, not %s" % type(was_quoted).__name__)
+    F = _check_fs(fs, quote, escape)
+    Q, E, special = _check_codec("requote_field_model", quote, escape, special)
+    value = bytes(value)
+    bare = set(special) | {F}
+    if E is None:
+        if not (was_quoted or any(b in bare or b == Q for b in value)):
+            return value
+        return bytes([Q]) + value.replace(bytes([Q]), bytes([Q, Q])) + bytes([Q])
+    front = {E} | ({Q} if Q is not None else bare)
+    body = b"".join(bytes([E, b]) if b in front else bytes([b]) for b in value)
+    if Q is not None and (was_quoted or any(b in bare for b in value)):
+        return bytes([Q]) + body + bytes([Q])
+    return body
+
+
 def _check_values(values, what):
     import torch
     if not isinstance(values, torch.Tensor):
@@ -841,6 +925,9 @@ def load_engine():
                                                 ctypes.POINTER(KxBatchStats), vp]
         lib.kx_run_records_fd_field_list.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.POINTER(KxFieldRange),
                                                      u32, ctypes.c_uint8, ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
+        lib.kx_run_batch_field_values.argtypes = [vp, vp, vp, u64, ctypes.POINTER(KxBatchFieldList), ctypes.POINTER(KxFieldCodec), vp, sz, vp, vp, vp,
+                                                  ctypes.POINTER(sz), ctypes.POINTER(KxBatchStats), vp]
+        lib.kx_run_records_fd_field_values.argtypes = lib.kx_run_records_fd_field_list.argtypes
         lib.kx_run_records_fd_fields.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), u32, ctypes.c_uint8,
                                                  ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
         lib.kx_run_records_fd_opts.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.c_int,
@@ -1294,10 +1381,11 @@ class Program:
             frame.suffix[:len(suffix)] = bytes(suffix)
         return self._run_batch_call("run_batch_tensor", values, offsets, out, frame, None)
 
-    def _run_batch_call(self, what, values, offsets, out, frame, fields):
+    def _run_batch_call(self, what, values, offsets, out, frame, fields, codec=None):
         """The device part of run_batch_tensor (`frame`: a KxBatchFrame or None), run_batch_fields_tensor (`fields`: a
-        KxBatchFields) and run_batch_field_list_tensor (`fields`: a KxBatchFieldList, which adds the fail_field tensor to the
-        result): the checks that need the tensors' device, the buffers, the size query and the call."""
+        KxBatchFields), run_batch_field_list_tensor (`fields`: a KxBatchFieldList, which adds the fail_field tensor to the
+        result) and run_batch_field_values_tensor (the same with `codec`: a KxFieldCodec): the checks that need the tensors'
+        device, the buffers, the size query and the call."""
         import torch
         if not values.is_cuda:
             raise EngineError("%s: values must be on a HIP device (there is no CPU fallback)" % what)
@@ -1322,7 +1410,13 @@ class Program:
             st = KxBatchStats()
             bptr = ctypes.c_void_p(buf.data_ptr() if buf is not None and buf.numel() else None)
             bcap = buf.numel() if buf is not None else 0
-            if listed:
+            if codec is not None:
+                rc = self._lib.kx_run_batch_field_values(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
+                                                         ctypes.byref(fields), ctypes.byref(codec), bptr, bcap,
+                                                         ctypes.c_void_p(out_off.data_ptr()), ctypes.c_void_p(docs.data_ptr()),
+                                                         ctypes.c_void_p(ffield.data_ptr()), ctypes.byref(ol), ctypes.byref(st),
+                                                         ctypes.c_void_p(stream))
+            elif listed:
                 rc = self._lib.kx_run_batch_field_list(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
                                                        ctypes.byref(fields), bptr, bcap, ctypes.c_void_p(out_off.data_ptr()),
                                                        ctypes.c_void_p(docs.data_ptr()), ctypes.c_void_p(ffield.data_ptr()),
@@ -1417,6 +1511,32 @@ class Program:
         spec.suffix[:len(suffix)] = bytes(suffix)
         return self._run_batch_call("run_batch_field_list_tensor", values, offsets, out, None, spec)
 
+    def run_batch_field_values_tensor(self, values, offsets, ranges, fs=b"\t", quote=None, escape=None, special=b"\n", sep_len=0,
+                                      last_whole=False, keep_sep=True, suffix=b"", out=None):
+        """Field mode on unquoted values (kx_run_batch_field_values): run_batch_field_list_tensor where the program runs on the
+        VALUE of every selected field (unquote_field_model) and the field is replaced by the spelling of the program's output
+        (requote_field_model, with the 0 to 8 `special` bytes).  Needs a `quote` or an `escape` byte.  Returns the six tensors of
+        run_batch_field_list_tensor; fail_pos counts inside the value."""
+        _check_batch_args(values, offsets)
+        ranges, sep_len = _check_field_ranges(ranges), _check_sep_len(sep_len)
+        f = _check_fs(fs, quote, escape)
+        q, e, special = _check_codec("run_batch_field_values_tensor", quote, escape, special)
+        for name, v in (("last_whole", last_whole), ("keep_sep", keep_sep)):
+            if not isinstance(v, bool):
+                raise TypeError("run_batch_field_values_tensor: %s must be True or False, not %s" % (name, type(v).__name__))
+        if not isinstance(suffix, (bytes, bytearray)):
+            raise TypeError("run_batch_field_values_tensor: suffix must be bytes of length 0 to 8, not %s" % type(suffix).__name__)
+        if len(suffix) > 8:
+            raise ValueError("run_batch_field_values_tensor: suffix must be 0 to 8 bytes, not %d" % len(suffix))
+        arr, nr = _field_range_array(ranges)
+        spec = KxBatchFieldList(size=ctypes.sizeof(KxBatchFieldList), n_ranges=nr, ranges=arr, fs=f, quote=-1 if q is None else q,
+                                escape=-1 if e is None else e, sep_len=sep_len, last_whole=1 if last_whole else 0,
+                                keep_sep=1 if keep_sep else 0, suffix_len=len(suffix))
+        spec.suffix[:len(suffix)] = bytes(suffix)
+        codec = KxFieldCodec(size=ctypes.sizeof(KxFieldCodec), n_special=len(special))
+        codec.special[:len(special)] = special
+        return self._run_batch_call("run_batch_field_values_tensor", values, offsets, out, None, spec, codec)
+
     def fields_kernel_stats(self):
         """kx_fields_stats: HIP-event times of field mode's own kernels, summed over this program's calls (collect_timing)."""
         st = KxFieldsKernelStats()
@@ -1460,6 +1580,22 @@ class Program:
                 self._lib.kx_set_config(self._h, ctypes.byref(self._cfg))
 
     @staticmethod
+    def _check_unquote(what, unquote, field, fields, quote, escape):
+        """The `unquote=` keyword of record mode: with `field` or `fields`, and with a `quote` or an `escape` → (field, fields),
+        where with `unquote` a `field=K` has become the list K-K."""
+        if not isinstance(unquote, bool):
+            raise TypeError("%s: unquote must be True or False, not %s" % (what, type(unquote).__name__))
+        if not unquote:
+            return field, fields
+        if field is None and fields is None:
+            raise ValueError("%s: unquote= needs field= or fields=" % what)
+        if quote is None and escape is None:
+            raise ValueError("%s: unquote= needs quote= or escape=" % what)
+        if field is not None and fields is None:
+            return None, [_check_field(field)]
+        return field, fields
+
+    @staticmethod
     def _check_rs_alone(rs, sep, quote, escape, what):
         """The `rs=` keyword of record mode: 1 to 8 bytes, with the default `sep` and neither `quote` nor `escape`."""
         rs = _check_rs(rs)
@@ -1470,7 +1606,7 @@ class Program:
         return rs
 
     def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None, batch_actions=True, rs=None, chomp=False, ors=b"",
-                    field=None, fs=b"\t", fields=None):
+                    field=None, fs=b"\t", fields=None, unquote=False):
         """Record mode on bytes: every record of `data` (split after each `sep` byte, kx_split_records on the device) is a
         whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage).  With a `quote` byte
         a separator inside quotes ends no record (kx_split_records_quoted from parity 0).  With an `escape` byte an escaped
@@ -1484,10 +1620,14 @@ class Program:
         separator is never part of the body, and follows the output unless `chomp`; a record with fewer fields gives a
         NoFieldError.  With `fields` (a parse_field_list result, or a sequence of ints and (lo, hi) pairs; not with `field`) the
         program runs on every field of the list (kx_run_batch_field_list, field_list_records_model): a record with a rejected
-        field gives a MatchError whose `field` is the lowest rejected field and whose `pos` counts inside it."""
+        field gives a MatchError whose `field` is the lowest rejected field and whose `pos` counts inside it.  With `unquote`
+        (with `field` or `fields`, and a `quote` or an `escape`) the program runs on the VALUE of every selected field and the
+        field is replaced by the spelling of its output (kx_run_batch_field_values with the separator as the special byte,
+        unquote_field_model, requote_field_model); `field=K` is then the list K-K, and `pos` counts inside the value."""
         if not isinstance(data, (bytes, bytearray, memoryview)):
             raise TypeError("run_records: data must be bytes, not %s" % type(data).__name__)
         chomp, ors = _check_chomp(chomp), _check_ors(ors)
+        field, fields = self._check_unquote("run_records", unquote, field, fields, quote, escape)
         if field is not None and fields is not None:
             raise ValueError("run_records: field= and fields= exclude each other")
         if field is not None:
@@ -1498,7 +1638,7 @@ class Program:
             _check_fs(fs, quote, escape, sep if rs is None else rs if len(rs) == 1 else None)
         if rs is not None:
             rs = self._check_rs_alone(rs, sep, quote, escape, "run_records")
-        _check_sep(sep)
+        sep_byte = bytes([_check_sep(sep)])              # (`sep` itself may be an int)
         if quote is not None:
             _check_quote(quote, sep)
         if escape is not None:
@@ -1529,7 +1669,11 @@ class Program:
         trim = (len(rs) if rs is not None else 1) if chomp else 0
         ffield = None
         with self._batch_actions_for_call(batch_actions):
-            if fields is not None:
+            if unquote:
+                out, ooff, status, fpos, fstage, ffield = self.run_batch_field_values_tensor(
+                    v, offs, fields, fs, quote, escape, special=sep_byte, sep_len=1, last_whole=bool(tail and data), keep_sep=not chomp,
+                    suffix=ors)
+            elif fields is not None:
                 out, ooff, status, fpos, fstage, ffield = self.run_batch_field_list_tensor(
                     v, offs, fields, fs, quote, escape, sep_len=len(rs) if rs is not None else 1, last_whole=bool(tail and data),
                     keep_sep=not chomp, suffix=ors)
@@ -1547,7 +1691,7 @@ class Program:
                 for i in range(len(status))]
 
     def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None, batch_actions=True, rs=None, chomp=False,
-                       ors=b"", field=None, fs=b"\t", fields=None):
+                       ors=b"", field=None, fs=b"\t", fields=None, unquote=False):
         """kx_run_records_fd: the stream on in_fd in record mode, outputs to out_fd, one line per rejected record to report_fd
         (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected.  With a `quote`
         byte, kx_run_records_fd_quoted: a separator inside quotes ends no record.  With an `escape` byte,
@@ -1557,7 +1701,9 @@ class Program:
         record's output.  With `field`, kx_run_records_fd_fields: the program runs on field `field` of every record (fields end at
         the live `fs` bytes), the rest of the record is copied; a record with fewer fields is reported and counts as rejected.
         With `fields` (as in run_records; not with `field`), kx_run_records_fd_field_list: the program runs on every field of the
-        list, and a record with a rejected field is reported once, with the field's number."""
+        list, and a record with a rejected field is reported once, with the field's number.  With `unquote` (as in run_records),
+        kx_run_records_fd_field_values: the program runs on the values of the selected fields, which are spelled again behind it."""
+        field, fields = self._check_unquote("run_records_fd", unquote, field, fields, quote, escape)
         for name, fd in (("in_fd", in_fd), ("out_fd", out_fd), ("report_fd", report_fd)):
             if isinstance(fd, bool) or not isinstance(fd, int):
                 raise TypeError("run_records_fd: %s must be an int file descriptor, not %s" % (name, type(fd).__name__))
@@ -1588,7 +1734,7 @@ class Program:
                     name, args = "kx_run_records_fd_fields", (ctypes.byref(o), field, f)
                 if fields is not None:
                     arr, nr = _field_range_array(fields)
-                    name, args = "kx_run_records_fd_field_list", (ctypes.byref(o), arr, nr, f)
+                    name, args = "kx_run_records_fd_field_values" if unquote else "kx_run_records_fd_field_list", (ctypes.byref(o), arr, nr, f)
             else:                                        # the mode's own entry point
                 name, args = (("kx_run_records_fd", (s,)), ("kx_run_records_fd_quoted", (s, q)), ("kx_run_records_fd_escaped", (s, qi, e)),
                               ("kx_run_records_fd_rs", (rs, len(rs or b""))))[mode]
