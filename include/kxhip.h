@@ -176,6 +176,37 @@ int kx_stage_delayed_form(const kx_program* prog, uint32_t stage);
 /* forget the back-off: the stage's next shard tries the delayed form again (no-op for a stage without one) */
 void kx_stage_reset_delayed_form(kx_program* prog, uint32_t stage);
 
+/* ---- what the loader builds for a stage (kleenexlang_amd/csrc/engine/kx_stage.h) --------------------------------------------
+ * kx_stage_describe_cfg needs no device: it runs the host-only stage builder as kx_load_config does (cfg NULL: all defaults) and
+ * reports the layout it decided, the scalar fields of the structs the kernels take, and the bytes of one of the stage's device
+ * allocations.  Every pointer field of those structs appears as its byte offset into the allocation it points into.  `image`, if
+ * not NULL, receives up to image_cap bytes of allocation `which`; info->image_bytes is its size (0: the stage has none, e.g. no
+ * job-stride alternative).  Set info->size = sizeof(kx_stage_info) before the call.  Returns 0, KX_E_BLOB or KX_E_ARG. */
+#define KX_STAGE_MAIN 0u     /* the general engine's tables (info->t describes them)                                         */
+#define KX_STAGE_ALT 1u      /* the same stage in the job-stride layout, where kx_load_config keeps both (info->t describes IT) */
+#define KX_STAGE_DELAYED 2u  /* the delayed form's table image | start_of_state                                              */
+#define KX_STAGE_SLOW 3u     /* the tables of the delayed form's exact slow path                                             */
+typedef struct kx_stage_info {
+  uint32_t size;           /* sizeof(kx_stage_info) */
+  uint32_t which;
+  uint64_t image_bytes;
+  uint32_t general, big, has_alt, has_df, actions, action_regs, max_const_len, reserved0;
+  uint64_t lds_bytes, sync_lds_bytes;
+  struct {                 /* the general engine's DevTables; packed … init_len: offsets into KX_STAGE_MAIN / KX_STAGE_ALT */
+    uint64_t packed, pair, wlen, cls, nleaves, fin_leaf, sync16, init_off, init_len;
+    uint32_t packed_words, off_fwd, off_ent, off_pool, off_cls, off_adesc, naid, nstates, nclasses, q0h, maxleaves, deadh, nullrow, cshift,
+        debug, big, hshift, rshift, rbase, stage_words, pair_words, pair_magic, nsync, sync_multi, sync_words, off_tbl, xlat, tblmode,
+        aid_mask, inl, jl, direct, short_consts, reserved0;
+  } t;
+  struct {                 /* the delayed form's DfDev (all zero without one); img, start_of_state: offsets into KX_STAGE_DELAYED;
+                              sl_nleaves, sl_fin_leaf, sl_cls: into KX_STAGE_MAIN; the other sl_*: into KX_STAGE_SLOW */
+    uint64_t img, start_of_state, sl_fmap, sl_back, sl_nleaves, sl_fin_leaf, sl_cls, sl_pcoff, sl_pcpool, sl_pend, sl_defoff, sl_defpc, sl_q;
+    uint32_t words, off_pool, deadh, esch, starth, K, C, orig_c4, hshift, short_consts, debug, nstates, J, wide, sl_Lm, sl_npc, sl_on, reserved0;
+  } d;
+} kx_stage_info;
+int kx_stage_describe_cfg(const void* blob, size_t blob_len, uint32_t stage, const kx_config* cfg, uint32_t which, kx_stage_info* info,
+                          void* image, size_t image_cap);
+
 /* Whole program (all pipeline stages) over one device-resident input.
  * d_out may be NULL with cap 0 to query the exact output size (returned in
  * *out_len with KX_E_CAPACITY).  Blocks until the result is complete. */

@@ -73,7 +73,7 @@ struct DfBuild {
   uint32_t indexOf(uint32_t handle) const { return (handle - DF_OFF_ROWS) / (C * 8); }
 };
 
-struct DfInput {   // views into a parsed stage (kx_engine.hip: parseStage)
+struct DfInput {   // views into a parsed stage (kx_stage.h: buildStage)
   uint32_t nstates, C, q0, Lm, nback, npc;
   const uint8_t* cls; const uint16_t* delta; const uint32_t* pback; const uint8_t* nleaves; const uint32_t* back;
   const uint32_t* pcoff; const uint8_t* pcpool; const uint32_t* init_const;

@@ -15,25 +15,7 @@
 // copied", bits 10-22 the constant's pool offset / 16, bit 23 "a constant follows", bits 24-30 bytes appended (copy included).
 // The copied byte of step s is input byte s-K.
 
-struct DfDev {
-  const uint32_t* img; uint32_t words;
-  uint32_t off_pool, deadh, esch, starth, K, C;
-  const uint16_t* start_of_state;     // [nstates] handle of (q, nothing pending), 0xFFFF = none
-  uint32_t orig_c4, hshift;           // the general tables' row size (C*4) and handle shift: k_sync's handles -> state ids
-  uint32_t short_consts, debug;
-  uint32_t nstates;                   // SST states: start_of_state's length
-  uint32_t J;                         // merge window (kx_delayed.h): a lane's own part starts K + J symbols behind its synchronisation point
-  uint32_t wide;                      // more than 31 byte classes: the class table holds class indices, the kernels shift by 3
-  // Round 6 — the EXACT SLOW PATH of a context that the delay does not decide (k_dforward: `slow`): the path form as the blob holds
-  // it, in global memory (sl_back[row * Lm + leaf] = parent | copy << 8 | constant << 9, 0xFFFFFFFF dead), and what a product state
-  // owes: sl_q its SST state, sl_pend[(state * K + j) * Lm + leaf] the kind (copy | constant << 1) of pending step j at that leaf,
-  // sl_defpc[sl_defoff[state] ..] the constants that are due.  sl_on = 0: the stage has none (more than 16 leaves): an escape
-  // sends the whole shard to the general engine as in round 5.
-  const uint4* sl_fmap;   // 3 x uint4 per (state, class): {next state | its leaves << 16, backward row, 0, 0} {parent leaf of leaves 0-15, a byte each, 0xFF dead} {… 16-31}
-  const uint32_t* sl_back; const uint8_t* sl_nleaves; const uint8_t* sl_fin_leaf; const uint8_t* sl_cls;
-  const uint32_t* sl_pcoff; const uint8_t* sl_pcpool; const uint32_t* sl_pend; const uint32_t* sl_defoff; const uint32_t* sl_defpc; const uint16_t* sl_q;
-  uint32_t sl_Lm, sl_npc, sl_on;
-};
+// (struct DfDev: kx_stage.h, with the host code that fills it)
 // A piece that the slow path resolved has no states to walk from: its record names a run of SIDE ENTRIES instead (one per path
 // step: bit 0 copy, bits 1-30 the constant (>= sl_npc: none), bit 31 an entry without an input byte — a constant that was due),
 // and k_demit's lane replays them straight into the output (a hole record, below).
@@ -53,7 +35,8 @@ constexpr uint32_t DF_HOLE_MAX = 4096, DF_HOLE_FIRST = 1024, DF_SL_LEAVES = 32;
 struct __attribute__((aligned(8))) DfRec { uint32_t x, y; };
 constexpr uint32_t DFREC_OWN = 0x80000000u, DFREC_HOLE = 0x80000000u, DFREC_HOLE_FIRST = 0x40000000u;
 constexpr uint32_t DF_MERGE_WINDOW_MAX = 64;   // the largest kx_config::merge_window (window J + 1)
-constexpr uint32_t DF_STEP_MAX = 126, DF_HOLE_LEN_MAX = 0xFFFFu, DF_HOLE_CNT_MAX = 0x3FFFu, DF_WBASE_PIECES = 32;
+using kxst::DF_STEP_MAX;   // (kx_stage.h: dfRecFits checks an image against it when a stage is loaded)
+constexpr uint32_t DF_HOLE_LEN_MAX = 0xFFFFu, DF_HOLE_CNT_MAX = 0x3FFFu, DF_WBASE_PIECES = 32;
 constexpr DfRec dfrec_pack(uint32_t start, uint32_t middle, uint32_t lenA, uint32_t len, uint32_t kA, uint32_t kB) {
   return DfRec{(start >> 3) | ((middle >> 3) << 13) | (kA << 26), len | (lenA << 13) | (kB << 25)};
 }
@@ -92,13 +75,6 @@ static_assert(PIECE + kxdf::DF_MAX_K + DF_MERGE_WINDOW_MAX <= DF_HOLE_CNT_MAX, "
 static_assert((uint64_t)MAX_SEG * DF_STEP_MAX < DFREC_OWN, "wave base: a block part's output stays below the own flag");
 static_assert(DF_WBASE_PIECES == HALF && 2 * DF_WBASE_PIECES == PIECE, "wave base: one word per wave-iteration of half pieces, two per iteration of pieces");
 }  // namespace dfrec_check
-// does a table image respect the record's widths?  (host side, at load: a stage whose image does not has no delayed form)
-inline bool dfRecFits(const uint32_t* img, uint32_t nrows, uint32_t C) {
-  if (256u + (uint64_t)nrows * C * 8u > 65536u) return false;          // every row handle below 64 KiB (and a multiple of 8 by construction)
-  for (size_t i = 0; i < (size_t)nrows * C; ++i) if ((img[64 + 2 * i + 1] >> 24) > DF_STEP_MAX) return false;
-  return true;
-}
-
 struct DfLds {
   const uint8_t* base; uint32_t csh;
   __device__ __forceinline__ uint32_t c8(uint32_t byte) const { return (uint32_t)base[byte] << csh; }

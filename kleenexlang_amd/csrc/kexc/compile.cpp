@@ -445,7 +445,7 @@ int kexc_emit_pipeline(int buffer_unit_bits, int cc_opt_level, void (*info)(cons
       for (uint32_t q = 0; q < P.nstates; ++q)
         if (t.final_act[q] != 0xFFFFFFFFu && t.final_act[q] < P.nactions)
           for (auto& m : t.actions[t.final_act[q]]) if (m.op == 4) bad("AppendTblI in a final action (no symbol to index with)");
-      // (a stage with register actions takes no table atoms — the engine's parseStage refuses the pair — and the engine's entries
+      // (a stage with register actions takes no table atoms — the engine's loader refuses the pair (kx_stage.h: chooseLayout) — and the engine's entries
       //  name at most KXP_ENGINE_TABLES tables: both go the written-out way)
       bool native_tables = uses_tables && !getenv("KEXC_LOWER_TABLES") && !P.has_actions && P.ntables <= KXP_ENGINE_TABLES;
       for (uint32_t k = 0; k < P.ntables; ++k) native_tables = native_tables && P.tbl_width[k] == 1;

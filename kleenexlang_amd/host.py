@@ -838,6 +838,42 @@ class KxDfInfo(ctypes.Structure):
                                                "escapes_start", "merge_window")] + [("reason", ctypes.c_char * 96)]
 
 
+class _KxStageTables(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in ("packed", "pair", "wlen", "cls", "nleaves", "fin_leaf", "sync16", "init_off", "init_len")] + \
+               [(k, ctypes.c_uint32) for k in ("packed_words", "off_fwd", "off_ent", "off_pool", "off_cls", "off_adesc", "naid", "nstates", "nclasses",
+                                               "q0h", "maxleaves", "deadh", "nullrow", "cshift", "debug", "big", "hshift", "rshift", "rbase",
+                                               "stage_words", "pair_words", "pair_magic", "nsync", "sync_multi", "sync_words", "off_tbl", "xlat",
+                                               "tblmode", "aid_mask", "inl", "jl", "direct", "short_consts", "reserved0")]
+
+
+class _KxStageDelayed(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in ("img", "start_of_state", "sl_fmap", "sl_back", "sl_nleaves", "sl_fin_leaf", "sl_cls", "sl_pcoff",
+                                               "sl_pcpool", "sl_pend", "sl_defoff", "sl_defpc", "sl_q")] + \
+               [(k, ctypes.c_uint32) for k in ("words", "off_pool", "deadh", "esch", "starth", "K", "C", "orig_c4", "hshift", "short_consts", "debug",
+                                               "nstates", "J", "wide", "sl_Lm", "sl_npc", "sl_on", "reserved0")]
+
+
+class KxStageInfo(ctypes.Structure):
+    """include/kxhip.h::kx_stage_info — what the loader builds for one stage (layout decision, DevTables `t`, DfDev `d`)."""
+    _fields_ = [("size", ctypes.c_uint32), ("which", ctypes.c_uint32), ("image_bytes", ctypes.c_uint64)] + \
+               [(k, ctypes.c_uint32) for k in ("general", "big", "has_alt", "has_df", "actions", "action_regs", "max_const_len", "reserved0")] + \
+               [("lds_bytes", ctypes.c_uint64), ("sync_lds_bytes", ctypes.c_uint64), ("t", _KxStageTables), ("d", _KxStageDelayed)]
+
+    def as_dict(self):
+        """every field but size / which / reserved, nested ones as "t.inl" """
+        out = {}
+        for k, _ in self._fields_:
+            v = getattr(self, k)
+            if isinstance(v, ctypes.Structure):
+                out.update({"%s.%s" % (k, f): getattr(v, f) for f, _ in v._fields_ if f != "reserved0"})
+            elif k not in ("size", "which", "reserved0"):
+                out[k] = v
+        return out
+
+
+KX_STAGE_MAIN, KX_STAGE_ALT, KX_STAGE_DELAYED, KX_STAGE_SLOW = 0, 1, 2, 3
+
+
 class KxFwdSummary(ctypes.Structure):
     _fields_ = [("synced", ctypes.c_uint32), ("end_state", ctypes.c_uint32),
                 ("head_len", ctypes.c_uint64), ("fail_pos", ctypes.c_uint64)]
@@ -907,6 +943,7 @@ def load_engine():
         lib.kx_df_pending.argtypes = [ctypes.c_char_p, sz, u32, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]
         cfgp = ctypes.POINTER(KxConfig)
         lib.kx_df_describe_cfg.argtypes = [ctypes.c_char_p, sz, u32, cfgp, ctypes.POINTER(KxDfInfo), vp, sz]
+        lib.kx_stage_describe_cfg.argtypes = [ctypes.c_char_p, sz, u32, cfgp, u32, ctypes.POINTER(KxStageInfo), vp, sz]
         lib.kx_df_pending_cfg.argtypes = [ctypes.c_char_p, sz, u32, cfgp, u32, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]
         lib.kx_df_deferred.argtypes = [ctypes.c_char_p, sz, u32, cfgp, u32, ctypes.c_void_p, sz, ctypes.POINTER(sz)]
         lib.kx_df_start_of_state.argtypes = [ctypes.c_char_p, sz, u32, cfgp, u32, ctypes.POINTER(u32)]
@@ -1131,6 +1168,24 @@ def df_describe(blob, stage=0, with_image=True, cfg=None):
         lib.kx_df_describe_cfg(blob, len(blob), stage, ctypes.byref(cfg), ctypes.byref(info), buf, info.image_bytes)
         img = buf.raw
     return info, img
+
+
+def stage_describe(blob, stage=0, which=KX_STAGE_MAIN, cfg=None, with_image=True):
+    """What the loader builds for a stage, on the host (no device needed): (KxStageInfo, bytes of allocation `which` or None if
+    the stage has none).  which: KX_STAGE_MAIN / _ALT / _DELAYED / _SLOW.  cfg as for df_describe."""
+    lib = load_engine()
+    blob = bytes(blob)
+    info = KxStageInfo(size=ctypes.sizeof(KxStageInfo))
+    cfg = config_from_env() if cfg is None else cfg
+    probe = ctypes.create_string_buffer(1 << 20) if with_image else None   # (most images fit: one call)
+    if lib.kx_stage_describe_cfg(blob, len(blob), stage, ctypes.byref(cfg), which, ctypes.byref(info), probe, (1 << 20) if with_image else 0):
+        raise EngineError(lib.kx_last_error().decode("utf-8", "replace"))
+    if not with_image or not info.image_bytes:
+        return info, None
+    if info.image_bytes > (1 << 20):
+        probe = ctypes.create_string_buffer(info.image_bytes)
+        lib.kx_stage_describe_cfg(blob, len(blob), stage, ctypes.byref(cfg), which, ctypes.byref(info), probe, info.image_bytes)
+    return info, probe.raw[:info.image_bytes]
 
 
 def df_pending(blob, stage, state, slot, cfg=None):

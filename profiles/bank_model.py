@@ -20,7 +20,7 @@ rows = st.pback[states[:n], cls].astype(np.int64)
 leaf = int(st.fin_leaf[q]); lin = np.zeros(n, dtype=np.int64)     # leaf the step is entered with (index into its row)
 for i in range(n - 1, -1, -1):
     lin[i] = leaf; leaf = int(st.back[rows[i], leaf]) & 0xFF
-# engine layout (parseStage): fwd word index = 64 + q*C + c ; ent rows packed in order, row length = last live leaf + 1
+# engine layout (kx_stage.h): fwd word index = 64 + q*C + c ; ent rows packed in order, row length = last live leaf + 1
 nback = st.back.shape[0]
 rl = [max([j + 1 for j in range(st.maxleaves) if st.back[b, j] != 0xFFFFFFFF] + [1]) for b in range(nback)]
 rowoff = np.concatenate([[0], np.cumsum(rl)])[:-1]

@@ -211,7 +211,7 @@ WIDE_ENTRY_PROGRAM = 'main := (~/a/ "%s" | /b/ | ~/c/ "<%s>")*\n' % ("x" * 300, 
 
 
 def layout_facts(blob):
-    """what parseStage (kx_engine.hip) decides a stage's layout from: byte classes, the most leaves of a state, path entries that
+    """what chooseLayout (kx_stage.h) decides a stage's layout from: byte classes, the most leaves of a state, path entries that
     append one byte / more than one, the longest constant + copied byte of an entry"""
     st = kxp.parse(blob)[0]
     back = st.back.ravel()
@@ -224,9 +224,9 @@ def layout_facts(blob):
 
 def layout_kind(blob, inline_consts=0, job_stride=0):
     """'inline', 'job-stride', 'general' or 'plain': the k_emit / k_backlen instance family of a stage of small tables.  A restatement of
-    parseStage's choice for the programs used here, not all of it: symbol tables (xlat), tables beyond LDS addressing (big),
-    KX_FORCE_BIG and the count of distinct constants are left out — none of these programs has them.  The engine's line names only
-    the job-stride layout: plain / inline / general rest on this function."""
+    chooseLayout's choice (kx_stage.h) for the programs used here, not all of it: symbol tables (xlat), tables beyond LDS addressing
+    (big), KX_FORCE_BIG and the count of distinct constants are left out — none of these programs has them.  The engine's debug line
+    names only the job-stride layout; test_the_restated_layout_meets_the_engines holds this function to the engine's own decision."""
     f = layout_facts(blob)
     small = f["C"] <= 64 and f["Lm"] <= 64 and f["widest"] < 127 and not f["tables"]
     if small and (inline_consts == 2 if inline_consts else f["one"] > 0 and f["one"] >= f["longer"]):
@@ -254,6 +254,22 @@ def test_layouts_and_leaf_counts_of_the_general_engine_cases():
     for p in ("iso_datetime_to_json", LEAVES_PROGRAM):
         st = kxp.parse(blob_of(p))[0]
         assert sum((int(c) + 15) // 16 for c in np.diff(st.pconst_off)) <= 64
+
+
+def engine_layout_kind(blob, inline_consts=0, job_stride=0):
+    """layout_kind's answer as the engine's loader gives it (kx_stage_describe_cfg: no device needed)"""
+    info, _ = host.stage_describe(blob, cfg=host.KxConfig(inline_consts=inline_consts, job_stride=job_stride), with_image=False)
+    return "inline" if info.t.inl else "job-stride" if info.t.jl else "general" if info.general else "plain"
+
+
+def test_the_restated_layout_meets_the_engines():
+    """every program and switch of test_layouts_and_leaf_counts_of_the_general_engine_cases, and the whole grid of the two switches"""
+    for prog in ("apache_log", INLINE_PROGRAM, CLASSES_PROGRAM, WIDE_ENTRY_PROGRAM, "iso_datetime_to_json", LEAVES_PROGRAM):
+        for inl in (0, 1, 2):
+            for jl in (0, 1, 2):
+                assert layout_kind(blob_of(prog), inl, jl) == engine_layout_kind(blob_of(prog), inl, jl), (prog[:40], inl, jl)
+        info, _ = host.stage_describe(blob_of(prog), cfg=host.KxConfig(), with_image=False)
+        assert info.t.maxleaves == layout_facts(blob_of(prog))["Lm"] and info.t.nclasses == layout_facts(blob_of(prog))["C"]
 
 
 # --------------------------------------------------------------------------------------------------------------- the inputs
