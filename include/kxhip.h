@@ -516,6 +516,34 @@ int kx_run_batch_field_values(kx_program* prog, const void* d_in, const uint64_t
 int kx_run_records_fd_field_values(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_field_range* ranges,
                                    uint32_t n_ranges, uint8_t fs, int report_fd, kx_records_stats* stats);
 
+/* ---- field mode on words: the fields are the runs of bytes between blanks, as awk's default splitting has them ----------------------
+ * kx_run_batch_field_words is kx_run_batch_field_list — with a codec, kx_run_batch_field_values — in everything not said here; the
+ * normative text is host.blank_field_list_records_model.  A BLANK is the byte 0x20 or 0x09.  A blank is LIVE under the rule that
+ * makes an `fs` byte live there: every one (quote = escape = -1); one at even parity of the `quote` bytes before it in the record;
+ * one that is unescaped and at even parity of the record's unescaped quotes.  The body's fields are its WORDS, the maximal runs of
+ * body bytes that are not live blanks, numbered from 1: a field is never empty, quotes and escapes stay in the word, and a body
+ * that is empty or all live blanks has 0 fields — d_docs[i] = {fields found, 2, 0} may hold 0, and d_fail_field[i] is then the
+ * list's first member.  An accepted record's output is its body with every selected word replaced (by the program's output, or
+ * with a codec by its spelling); every other byte is copied as it is, every blank included — leading, trailing or repeated.
+ *   list->fs must be 0 (the struct keeps its layout; the field is not used).
+ *   codec may be NULL: the program runs on the raw words.  With a codec the value rule is unchanged and the spelling is
+ *     requote_field_model's with fs = the space and `special` = the codec's bytes plus the tab, which the library appends: with a
+ *     quote, an output that holds a blank is wrapped in quotes; with an escape and no quote, every blank of it gets an escape byte.
+ * KX_E_ARG besides kx_run_batch_field_list's and, with a codec, kx_run_batch_field_values's, all before any device work: fs != 0;
+ * a quote, an escape or a special byte that is a blank; n_special > 7. */
+int kx_run_batch_field_words(kx_program* prog, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* list,
+                             const kx_field_codec* codec, void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs,
+                             uint32_t* d_fail_field, size_t* out_len, kx_batch_stats* stats, void* stream);
+
+/* kx_run_records_fd_field_list on words (`BIN --records … --field=K|LIST --blanks [--unquote]`): every record goes through
+ * kx_run_batch_field_words with ranges[0, n_ranges) — without a codec, or with unquote != 0 with special = {o->sep}.  The report lines
+ * are kx_run_records_fd_field_list's; a record without any word reports "Record R has no field K!" with K the list's first member.
+ * KX_E_ARG: kx_run_records_fd_opts's, a list that is not in normal form, a one-byte record separator (sep, or rs with rs_len = 1),
+ * a quote or an escape byte of the mode that is a blank (a byte of a multi-byte rs may be one), and unquote != 0 in a mode other
+ * than KX_RECORDS_QUOTED and KX_RECORDS_ESCAPED. */
+int kx_run_records_fd_field_words(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_field_range* ranges,
+                                  uint32_t n_ranges, int unquote, int report_fd, kx_records_stats* stats);
+
 /* ---- sharded execution: one contiguous shard of the input per GPU -------------
  * Per stage and per rank:
  *   kx_shard_begin → kx_shard_forward → [exchange kx_fwd_summary] → kx_shard_fix_head

@@ -32,10 +32,12 @@ int checkFieldList(const kx_batch_field_list& l, const char* who) {
 // entry point, whose checks of `l` and `codec` have passed).  With a codec the documents the program runs on are the fields' VALUES
 // — k_fvdeclen, a scan and k_fvdecode take k_fgather's place — and k_fvenclen, a scan and k_fvencode spell the program's outputs
 // before k_flsplen and k_flsplice, which then take the spellings and their offsets for the outputs and theirs (kx_field_values.inc).
-// Without one, the kernels and their arguments are the list's own.
+// Without one, the kernels and their arguments are the list's own.  With `words` (kx_run_batch_field_words, kx_field_words_host.inc)
+// the fields are the body's words: k_fwcount and k_fwlocate (kx_field_words.inc) take the place of k_flcount and k_fllocate, l->fs
+// is not used, and the value kernels' field separator is the space.  Nothing else differs.
 int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* l,
                  const kx_field_codec* codec, void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs, uint32_t* d_fail_field,
-                 size_t* out_len, kx_batch_stats* stats, void* stream, const char* who) {
+                 size_t* out_len, kx_batch_stats* stats, void* stream, const char* who, bool words = false) {
   if (n_docs && (!d_in_off || !d_out_off || !d_docs)) return setErr(KX_E_ARG, std::string(who) + ": offsets, output offsets and document records are required");
   if (n_docs >= 0xFFFFFFFFull) return setErr(KX_E_ARG, std::string(who) + ": at most 2^32 - 2 documents per call");
   *out_len = 0;
@@ -118,7 +120,8 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
   const int mode = l->escape >= 0 ? FLD_ESCAPED : l->quote >= 0 ? FLD_QUOTED : FLD_PLAIN;
   // 1. the records' documents: how many, and the first one's index
   if (timing) HIPCHECK(hipEventRecord(W.ev[0], sm));
-  auto* const count = mode == FLD_ESCAPED ? &k_flcount<FLD_ESCAPED> : mode == FLD_QUOTED ? &k_flcount<FLD_QUOTED> : &k_flcount<FLD_PLAIN>;
+  auto* const count = words ? (mode == FLD_ESCAPED ? &k_fwcount<FLD_ESCAPED> : mode == FLD_QUOTED ? &k_fwcount<FLD_QUOTED> : &k_fwcount<FLD_PLAIN>)
+                            : (mode == FLD_ESCAPED ? &k_flcount<FLD_ESCAPED> : mode == FLD_QUOTED ? &k_flcount<FLD_QUOTED> : &k_flcount<FLD_PLAIN>);
   hipLaunchKernelGGL(count, dim3(bgrid), dim3(FLD_BT), 0, sm, in, off, (unsigned long long)nd, L, cnt, nf);
   if (timing) HIPCHECK(hipEventRecord(W.ev[1], sm));
   scanLens(cnt, nd, d0);
@@ -146,12 +149,13 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
     FVSpec C{};           // with a codec only: the bytes of the value kernels, and their grid (lane = document)
     uint32_t dgrid = 0;
     if (V) {
-      C = FVSpec{l->fs, L.F.quote, L.F.escape, codec->n_special, 0ull};
+      C = FVSpec{words ? 0x20u : (uint32_t)l->fs, L.F.quote, L.F.escape, codec->n_special, 0ull};
       for (uint32_t i = 0; i < C.nsp; ++i) C.sp8 |= (unsigned long long)codec->special[i] << (8 * i);
       dgrid = (uint32_t)std::min<uint64_t>((ndocs + FLD_BT - 1) / FLD_BT, (uint64_t)p->ncu * 4);
     }
     if (timing) HIPCHECK(hipEventRecord(W.ev[3], sm));
-    auto* const locate = mode == FLD_ESCAPED ? &k_fllocate<FLD_ESCAPED> : mode == FLD_QUOTED ? &k_fllocate<FLD_QUOTED> : &k_fllocate<FLD_PLAIN>;
+    auto* const locate = words ? (mode == FLD_ESCAPED ? &k_fwlocate<FLD_ESCAPED> : mode == FLD_QUOTED ? &k_fwlocate<FLD_QUOTED> : &k_fwlocate<FLD_PLAIN>)
+                               : (mode == FLD_ESCAPED ? &k_fllocate<FLD_ESCAPED> : mode == FLD_QUOTED ? &k_fllocate<FLD_QUOTED> : &k_fllocate<FLD_PLAIN>);
     hipLaunchKernelGGL(locate, dim3(bgrid), dim3(FLD_BT), 0, sm, in, off, (unsigned long long)nd, L, (const unsigned long long*)d0, fb, fe, len);
     if (timing) HIPCHECK(hipEventRecord(W.ev[4], sm));
     scanLens(len, ndocs, coff);

@@ -26,7 +26,8 @@
 // separator kept behind the record's output.  A record without the field is reported in a line of its own kind.  With a list of
 // fields (kx_run_records_fd_field_list) it calls kx_run_batch_field_list the same way; the report lines name the field.  On unquoted
 // values (kx_run_records_fd_field_values) it calls kx_run_batch_field_values with the list and a codec whose one special byte is the
-// record separator.
+// record separator.  On words (kx_run_records_fd_field_words) it calls kx_run_batch_field_words with the list, fs = 0 and, with
+// `unquote`, that codec; checkRecordsOpts has the blank rules.
 
 namespace {
 
@@ -242,6 +243,7 @@ struct RecordsRun {
   kx_field_range ranges[8] = {};                       // field mode with a list: the program runs on the fields of ranges[0, n_ranges)
   uint32_t n_ranges = 0;                               //   (0: no list; `field` is 0 with a list)
   kx_field_codec codec{};                              // ... on their values (size != 0: kx_run_batch_field_values; special = the separator)
+  bool words = false;                                  // ... which are the body's words (kx_run_batch_field_words; fsep is not used)
   SplitCarry next;                                     // what the next window's split starts from
   int report_fd = -1;
   RecWs ws;
@@ -298,12 +300,15 @@ struct RecordsRun {
     fl.suffix_len = o.ors_len;
     memcpy(fl.suffix, o.ors, o.ors_len);
     kx_batch_field_list ll{};
-    ll.size = sizeof ll; ll.n_ranges = n_ranges; ll.fs = fsep;
+    ll.size = sizeof ll; ll.n_ranges = n_ranges; ll.fs = words ? (uint8_t)0 : fsep;
     memcpy(ll.ranges, ranges, sizeof ll.ranges);
     ll.quote = fl.quote; ll.escape = fl.escape; ll.sep_len = fl.sep_len; ll.last_whole = fl.last_whole; ll.keep_sep = fl.keep_sep;
     ll.suffix_len = fl.suffix_len;
     memcpy(ll.suffix, fl.suffix, sizeof ll.suffix);
     auto run = [&](void* d_out, size_t cap, size_t* ol, kx_batch_stats* bs) {
+      if (n_ranges && words)
+        return kx_run_batch_field_words(p, in, d_o, ndocs, &ll, codec.size ? &codec : nullptr, d_out, cap, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p,
+                                        (uint32_t*)ffield.p, ol, bs, nullptr);
       if (n_ranges && codec.size)
         return kx_run_batch_field_values(p, in, d_o, ndocs, &ll, &codec, d_out, cap, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p, (uint32_t*)ffield.p, ol,
                                          bs, nullptr);
@@ -526,8 +531,9 @@ extern "C" int kx_split_records_rs(const void* d_in, size_t n, const uint8_t* rs
 
 namespace {
 
-// the rules of the six kx_run_records_fd* entry points (`who`); fs: the field separator of field mode, or -1
-int checkRecordsOpts(const kx_records_opts& o, const char* who, int fs = -1) {
+// the rules of the kx_run_records_fd* entry points (`who`); fs: the field separator of field mode, or -1; blanks: the fields are
+// the words between blanks (fs = -1), which the one-byte record separator, the quote and the escape byte of the mode cannot be
+int checkRecordsOpts(const kx_records_opts& o, const char* who, int fs = -1, bool blanks = false) {
   auto no = [&](const char* what) { return setErr(KX_E_ARG, std::string(who) + ": " + what); };
   if (o.size != sizeof(kx_records_opts)) return no("kx_records_opts::size is not this library's");
   if (o.pad[0] || o.pad[1] || o.pad[2]) return no("reserved words must be 0");
@@ -535,6 +541,13 @@ int checkRecordsOpts(const kx_records_opts& o, const char* who, int fs = -1) {
   if (o.ors_len > 8) return no("the output separator is at most 8 bytes");
   if (o.chomp > 1) return no("chomp must be 0 or 1");
   if (const int rc = checkSplit(o, SplitCarry{}, who)) return rc;
+  if (blanks) {
+    auto blank = [](int b) { return b == 0x20 || b == 0x09; };
+    if (o.mode != KX_RECORDS_RS && blank(o.sep)) return no("the record separator cannot be a blank");
+    if (o.mode == KX_RECORDS_RS && o.rs_len == 1 && blank(o.rs[0])) return no("the record separator cannot be a blank");
+    if ((o.mode == KX_RECORDS_QUOTED || o.mode == KX_RECORDS_ESCAPED) && blank(o.quote)) return no("the quote byte cannot be a blank");
+    if (o.mode == KX_RECORDS_ESCAPED && blank(o.escape)) return no("the escape byte cannot be a blank");
+  }
   if (fs < 0) return 0;
   if (o.mode != KX_RECORDS_RS && fs == (int)o.sep) return no("the field separator cannot be the record separator");
   if (o.mode == KX_RECORDS_RS && o.rs_len == 1 && fs == (int)o.rs[0]) return no("the field separator cannot be the record separator");
@@ -545,7 +558,7 @@ int checkRecordsOpts(const kx_records_opts& o, const char* who, int fs = -1) {
 
 // the stream on in_fd in record mode as `o` says (checkRecordsOpts has passed)
 int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o, int report_fd, kx_records_stats* stats, uint32_t field = 0,
-                 uint8_t fsep = 0, const kx_field_range* ranges = nullptr, uint32_t n_ranges = 0, bool values = false) {
+                 uint8_t fsep = 0, const kx_field_range* ranges = nullptr, uint32_t n_ranges = 0, bool values = false, bool words = false) {
   if (!p) return setErr(KX_E_ARG, "null argument");
   if (p->cfg.phase) return setErr(KX_E_ARG, "record mode runs every phase: kx_config::phase must be 0");
   const double t_begin = FdStream::nowMs();
@@ -559,7 +572,7 @@ int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o,
   (void)hipGetDevice(&fsr.dev);
   RecordsRun R;
   R.p = p; R.fs = &fsr; R.o = o; R.report_fd = report_fd; R.field = field; R.fsep = fsep;
-  R.n_ranges = n_ranges;
+  R.n_ranges = n_ranges; R.words = words;
   if (n_ranges) memcpy(R.ranges, ranges, n_ranges * sizeof(kx_field_range));
   if (values) { R.codec.size = sizeof R.codec; R.codec.n_special = 1; R.codec.special[0] = o.sep; }
   R.timing = p->cfg.collect_timing != 0;
@@ -639,4 +652,15 @@ extern "C" int kx_run_records_fd_field_values(kx_program* p, int in_fd, int out_
   if (const int rc = checkRecordsOpts(*o, who, fs)) return rc;
   if (o->mode != KX_RECORDS_QUOTED && o->mode != KX_RECORDS_ESCAPED) return setErr(KX_E_ARG, std::string(who) + ": values need a quote or an escape byte");
   return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, 0, fs, ranges, n_ranges, true);
+}
+
+extern "C" int kx_run_records_fd_field_words(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_field_range* ranges,
+                                             uint32_t n_ranges, int unquote, int report_fd, kx_records_stats* stats) {
+  static const char* const who = "kx_run_records_fd_field_words";
+  if (!o || !ranges) return setErr(KX_E_ARG, "null argument");
+  if (!kxFieldListIsNormal(ranges, n_ranges))
+    return setErr(KX_E_ARG, std::string(who) + ": the field list is not in normal form (1 to 8 ranges: sorted, disjoint, not adjacent, only the last open)");
+  if (const int rc = checkRecordsOpts(*o, who, -1, true)) return rc;
+  if (unquote && o->mode != KX_RECORDS_QUOTED && o->mode != KX_RECORDS_ESCAPED) return setErr(KX_E_ARG, std::string(who) + ": values need a quote or an escape byte");
+  return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, 0, 0, ranges, n_ranges, unquote != 0, true);
 }

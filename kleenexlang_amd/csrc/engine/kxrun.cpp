@@ -23,8 +23,10 @@
 // plain number) the program runs on every field of the list, each a whole input of its own, and the record is written only if all
 // of them are accepted (kx_run_records_fd_field_list; the list's parser is kx_field_list.h).  With `--unquote` (with --field, and
 // --quote or --escape) the program runs on the VALUE of each selected field, and the field is replaced by the spelling of its
-// output, quoted and escaped as it needs (kx_run_records_fd_field_values; --field=K is then the list K-K).  What --field, --fs and
-// --unquote refuse exits with status 2.
+// output, quoted and escaped as it needs (kx_run_records_fd_field_values; --field=K is then the list K-K).  With `--blanks` (with
+// --field, not with --fs) the fields are the words between runs of live spaces and tabs, as awk's default splitting has them, and
+// every blank is copied as it is (kx_run_records_fd_field_words; --field=K is then the list K-K, with or without --unquote).  What
+// --field, --fs, --unquote and --blanks refuse exits with status 2.
 //
 // BIN = this executable ++ KXP blob ++ libdir ++ trailer (see kexc main.cpp).
 // The engine is loaded with dlopen so that this file carries no HIP dependency.
@@ -91,6 +93,7 @@ static void usage(const char* name) {
   fprintf(stdout, "- \"%s --records ... --field=K [--fs=F]\": runs field K (from 1; fields end at F, default a tab) of every record, the rest is copied.\n", name);
   fprintf(stdout, "- \"%s --records ... --field=LIST [--fs=F]\": the same on every field of LIST (2,5-7,9-); a record is written only if all of them are accepted.\n", name);
   fprintf(stdout, "- \"%s --records ... --quote|--escape --field=K|LIST [--fs=F] --unquote\": the program runs on the unquoted value of every selected field; its output is quoted again as it needs.\n", name);
+  fprintf(stdout, "- \"%s --records ... --field=K|LIST --blanks [--unquote]\": the fields are the words between runs of spaces and tabs (awk's default); every blank is copied as it is.\n", name);
 }
 
 // --records=SEP, --quote=Q, --escape=E: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
@@ -176,11 +179,11 @@ int main(int argc, char** argv) {
                                          {"escape", optional_argument, 0, 'e'}, {"rs", required_argument, 0, 's'},
                                          {"chomp", no_argument, 0, 'c'}, {"ors", required_argument, 0, 'o'},
                                          {"field", required_argument, 0, 'f'}, {"fs", required_argument, 0, 'F'},
-                                         {"unquote", no_argument, 0, 'u'}, {0, 0, 0, 0}};
+                                         {"unquote", no_argument, 0, 'u'}, {"blanks", no_argument, 0, 'b'}, {0, 0, 0, 0}};
   bool timing = false, records = false, quoted = false, escaped = false, sep_given = false, multi = false, chomp = false, ors_given = false;
   uint8_t sep = '\n', quote = '"', escape = '\\', rs[8] = {}, ors[8] = {};
   uint32_t rs_len = 0, ors_len = 0, field = 0;
-  bool field_given = false, fs_given = false, unquote = false;
+  bool field_given = false, fs_given = false, unquote = false, blanks = false;
   kx_field_range ranges[KX_FIELD_RANGES] = {};   // --field=LIST in normal form (n_ranges = 0: --field=K, one plain number)
   uint32_t n_ranges = 0;
   uint8_t fsep = '\t';
@@ -242,6 +245,7 @@ int main(int argc, char** argv) {
         if (!parseSeparator(optarg, &fsep)) { fprintf(stderr, "Invalid --fs: %s (one byte)\n", optarg); return 2; }
         break;
       case 'u': unquote = true; break;
+      case 'b': blanks = true; break;
       case 'h':
       default: usage(argv[0]); return 1;
     }
@@ -260,13 +264,19 @@ int main(int argc, char** argv) {
   if (chomp && !records) { fprintf(stderr, "%s: --chomp needs --records\n", argv[0]); return 1; }
   if (ors_given && !records) { fprintf(stderr, "%s: --ors needs --records\n", argv[0]); return 1; }
   if (field_given && !records) { fprintf(stderr, "%s: --field needs --records\n", argv[0]); return 2; }
+  auto isBlank = [](uint8_t b) { return b == ' ' || b == '\t'; };
+  if (blanks && !field_given) { fprintf(stderr, "%s: --blanks needs --field\n", argv[0]); return 2; }
+  if (blanks && fs_given) { fprintf(stderr, "%s: --blanks cannot be combined with --fs\n", argv[0]); return 2; }
+  if (blanks && (multi ? rs_len == 1 && isBlank(rs[0]) : isBlank(sep))) { fprintf(stderr, "%s: with --blanks the record separator cannot be a space or a tab\n", argv[0]); return 2; }
+  if (blanks && quoted && isBlank(quote)) { fprintf(stderr, "%s: with --blanks the --quote character cannot be a space or a tab\n", argv[0]); return 2; }
+  if (blanks && escaped && isBlank(escape)) { fprintf(stderr, "%s: with --blanks the --escape character cannot be a space or a tab\n", argv[0]); return 2; }
   if (fs_given && !field_given) { fprintf(stderr, "%s: --fs needs --field\n", argv[0]); return 2; }
   if (field_given && (multi ? rs_len == 1 && fsep == rs[0] : fsep == sep)) { fprintf(stderr, "%s: --fs cannot be the record separator\n", argv[0]); return 2; }
   if (field_given && quoted && fsep == quote) { fprintf(stderr, "%s: --fs cannot be the --quote character\n", argv[0]); return 2; }
   if (field_given && escaped && fsep == escape) { fprintf(stderr, "%s: --fs cannot be the --escape character\n", argv[0]); return 2; }
   if (unquote && !field_given) { fprintf(stderr, "%s: --unquote needs --field\n", argv[0]); return 2; }
   if (unquote && !quoted && !escaped) { fprintf(stderr, "%s: --unquote needs --quote or --escape\n", argv[0]); return 2; }
-  if (unquote && !n_ranges) { ranges[0] = kx_field_range{field, field}; n_ranges = 1; }   // --field=K on values: the list K-K
+  if ((unquote || blanks) && !n_ranges) { ranges[0] = kx_field_range{field, field}; n_ranges = 1; }   // --field=K on values or words: the list K-K
   struct timeval t0, t1;
   if (timing) gettimeofday(&t0, nullptr);
 
@@ -290,13 +300,15 @@ int main(int argc, char** argv) {
     decltype(&kx_run_records_fd_opts) runo = nullptr;
     decltype(&kx_run_records_fd_fields) runf = nullptr;
     decltype(&kx_run_records_fd_field_list) runl = nullptr;
+    decltype(&kx_run_records_fd_field_words) runw = nullptr;
     if (!runr) return 1;
     if (quoted && !(runq = (decltype(runq))engineSymbol(h, argv[0], "kx_run_records_fd_quoted", "--quote needs"))) return 1;
     if (escaped && !(rune = (decltype(rune))engineSymbol(h, argv[0], "kx_run_records_fd_escaped", "--escape needs"))) return 1;
     if (multi && !(runm = (decltype(runm))engineSymbol(h, argv[0], "kx_run_records_fd_rs", "--rs needs"))) return 1;
     if (field_given && !n_ranges && !(runf = (decltype(runf))engineSymbol(h, argv[0], "kx_run_records_fd_fields", "--field needs"))) return 1;
-    if (n_ranges && !unquote && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_list", "--field=LIST needs"))) return 1;
-    if (unquote && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_values", "--unquote needs"))) return 1;   // (the same signature)
+    if (blanks && !(runw = (decltype(runw))engineSymbol(h, argv[0], "kx_run_records_fd_field_words", "--blanks needs"))) return 1;
+    if (n_ranges && !unquote && !blanks && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_list", "--field=LIST needs"))) return 1;
+    if (unquote && !blanks && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_values", "--unquote needs"))) return 1;   // (the same signature)
     if (framing && !(runo = (decltype(runo))engineSymbol(h, argv[0], "kx_run_records_fd_opts", "--chomp and --ors need"))) return 1;
     // record mode is where the single-document route is unusable (a third of a millisecond per record): stages with register
     // actions are replayed by the batch kernels unless KX_BATCH_ACTIONS=0 asks for the route
@@ -314,7 +326,8 @@ int main(int argc, char** argv) {
       memcpy(o.rs, rs, 8); o.rs_len = rs_len;
       o.chomp = chomp ? 1u : 0u;
       memcpy(o.ors, ors, 8); o.ors_len = ors_len;
-      rc = n_ranges    ? runl(prog, STDIN_FILENO, STDOUT_FILENO, &o, ranges, n_ranges, fsep, STDERR_FILENO, &rs_stats)
+      rc = blanks      ? runw(prog, STDIN_FILENO, STDOUT_FILENO, &o, ranges, n_ranges, unquote ? 1 : 0, STDERR_FILENO, &rs_stats)
+           : n_ranges  ? runl(prog, STDIN_FILENO, STDOUT_FILENO, &o, ranges, n_ranges, fsep, STDERR_FILENO, &rs_stats)
            : field_given ? runf(prog, STDIN_FILENO, STDOUT_FILENO, &o, field, fsep, STDERR_FILENO, &rs_stats)
                        : runo(prog, STDIN_FILENO, STDOUT_FILENO, &o, STDERR_FILENO, &rs_stats);
     } else if (multi) rc = runm(prog, STDIN_FILENO, STDOUT_FILENO, rs, rs_len, STDERR_FILENO, &rs_stats);

@@ -668,6 +668,82 @@ def field_list_records_model(data, offsets, sep_len, last_whole, ranges, fs, quo
     return res
 
 
+BLANKS = b" \t"                                                 # the blanks of `--blanks`: 0x20 and 0x09
+
+
+def _check_not_blank(quote=None, escape=None, sep=None, special=b""):
+    """The bytes of a `blanks=` call that cannot be a blank: the quote, the escape, the one-byte record separator `sep` and the
+    special bytes."""
+    for what, v in (("quote character", quote), ("escape character", escape), ("record separator", sep)):
+        if v is not None and _one_byte(v, what) in BLANKS:
+            raise ValueError("%s: %r is a blank, which blanks= makes a field separator" % (what, bytes([_one_byte(v, what)])))
+    if any(b in BLANKS for b in special):
+        raise ValueError("special: a special byte cannot be a blank with blanks=")
+
+
+def blank_field_list_records_model(data, offsets, sep_len, last_whole, ranges, quote=None, escape=None):
+    """kx_run_batch_field_words's view of its records in pure Python — the normative model of `--field=LIST --blanks`.  The
+    records and their bodies are field_records_model's; `ranges` is the list (what `fields=` takes).  A BLANK is the byte 0x20 or
+    0x09.  A blank is LIVE under the rule that makes an `fs` byte live there: every one; with a `quote` byte one at even parity of
+    the quote bytes before it in the record; with an `escape` byte one that is unescaped and at even parity of the record's
+    unescaped quotes (an escaped byte is only data).  The body's fields are its WORDS: the maximal runs of body bytes that are not
+    live blanks, numbered from 1.  A field is never empty, quotes and escapes stay in the word, and a body that is empty or all
+    live blanks has 0 fields.  The return shape is field_list_records_model's: a record with at least field_list_need(ranges) words
+    gives (gaps, fields, separator) — `fields` the m selected (K, bytes) pairs in order, `gaps` the m + 1 byte strings around them,
+    every blank of the body in one of them — and a record with fewer gives the number of words it has."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError("blank_field_list_records_model: data must be bytes, not %s" % type(data).__name__)
+    sep_len, ranges = _check_sep_len(sep_len), _check_field_ranges(ranges)
+    if not isinstance(last_whole, bool):
+        raise TypeError("blank_field_list_records_model: last_whole must be True or False, not %s" % type(last_whole).__name__)
+    _check_not_blank(quote, escape)
+    q = None if quote is None else _one_byte(quote, "quote character")
+    e = None if escape is None else _one_byte(escape, "escape character")
+    if q is not None and q == e:
+        raise ValueError("escape character: %r is also the quote character" % bytes([e]))
+    data, offs = bytes(data), [int(o) for o in offsets]
+    check_batch_offsets(offs, len(data))
+    need = field_list_need(ranges)
+    n, res = len(offs) - 1, []
+    for i in range(n):
+        t = 0 if last_whole and i == n - 1 else sep_len
+        if offs[i + 1] - offs[i] < t:
+            raise ValueError("blank_field_list_records_model: record %d is shorter than its separator (%d)" % (i, t))
+        body, sep = data[offs[i]:offs[i + 1] - t], data[offs[i + 1] - t:offs[i + 1]]
+        words, begin, parity, esc = [], None, 0, False        # the words as (begin, end); begin: of the word the walk is in
+        for k, b in enumerate(body):
+            live = False
+            if esc:
+                esc = False
+            elif e is not None and b == e:
+                esc = True
+            elif q is not None and b == q:
+                parity ^= 1
+            elif b in BLANKS and parity == 0:
+                live = True
+            if not live and begin is None:
+                begin = k
+            elif live and begin is not None:
+                words.append((begin, k))
+                begin = None
+        if begin is not None:
+            words.append((begin, len(body)))
+        nf = len(words)
+        if nf < need:
+            res.append(nf)
+            continue
+        gaps, fields, at = [], [], 0
+        for lo, hi in ranges:
+            for K in range(lo, (nf if hi is None else hi) + 1):
+                wb, we = words[K - 1]
+                gaps.append(body[at:wb])
+                fields.append((K, body[wb:we]))
+                at = we
+        gaps.append(body[at:])
+        res.append((gaps, fields, sep))
+    return res
+
+
 class KxFieldCodec(ctypes.Structure):
     """include/kxhip.h::kx_field_codec."""
     _fields_ = [("size", ctypes.c_uint32), ("n_special", ctypes.c_uint32), ("special", ctypes.c_uint8 * 8), ("reserved", ctypes.c_uint32 * 4)]
@@ -965,6 +1041,9 @@ def load_engine():
         lib.kx_run_batch_field_values.argtypes = [vp, vp, vp, u64, ctypes.POINTER(KxBatchFieldList), ctypes.POINTER(KxFieldCodec), vp, sz, vp, vp, vp,
                                                   ctypes.POINTER(sz), ctypes.POINTER(KxBatchStats), vp]
         lib.kx_run_records_fd_field_values.argtypes = lib.kx_run_records_fd_field_list.argtypes
+        lib.kx_run_batch_field_words.argtypes = lib.kx_run_batch_field_values.argtypes
+        lib.kx_run_records_fd_field_words.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.POINTER(KxFieldRange),
+                                                      u32, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
         lib.kx_run_records_fd_fields.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), u32, ctypes.c_uint8,
                                                  ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
         lib.kx_run_records_fd_opts.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.c_int,
@@ -1436,11 +1515,11 @@ class Program:
             frame.suffix[:len(suffix)] = bytes(suffix)
         return self._run_batch_call("run_batch_tensor", values, offsets, out, frame, None)
 
-    def _run_batch_call(self, what, values, offsets, out, frame, fields, codec=None):
+    def _run_batch_call(self, what, values, offsets, out, frame, fields, codec=None, words=False):
         """The device part of run_batch_tensor (`frame`: a KxBatchFrame or None), run_batch_fields_tensor (`fields`: a
         KxBatchFields), run_batch_field_list_tensor (`fields`: a KxBatchFieldList, which adds the fail_field tensor to the
-        result) and run_batch_field_values_tensor (the same with `codec`: a KxFieldCodec): the checks that need the tensors'
-        device, the buffers, the size query and the call."""
+        result), run_batch_field_values_tensor (the same with `codec`: a KxFieldCodec) and run_batch_field_words_tensor (`words`;
+        `codec` a KxFieldCodec or None): the checks that need the tensors' device, the buffers, the size query and the call."""
         import torch
         if not values.is_cuda:
             raise EngineError("%s: values must be on a HIP device (there is no CPU fallback)" % what)
@@ -1465,7 +1544,13 @@ class Program:
             st = KxBatchStats()
             bptr = ctypes.c_void_p(buf.data_ptr() if buf is not None and buf.numel() else None)
             bcap = buf.numel() if buf is not None else 0
-            if codec is not None:
+            if words:
+                rc = self._lib.kx_run_batch_field_words(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
+                                                        ctypes.byref(fields), ctypes.byref(codec) if codec is not None else None, bptr,
+                                                        bcap, ctypes.c_void_p(out_off.data_ptr()), ctypes.c_void_p(docs.data_ptr()),
+                                                        ctypes.c_void_p(ffield.data_ptr()), ctypes.byref(ol), ctypes.byref(st),
+                                                        ctypes.c_void_p(stream))
+            elif codec is not None:
                 rc = self._lib.kx_run_batch_field_values(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
                                                          ctypes.byref(fields), ctypes.byref(codec), bptr, bcap,
                                                          ctypes.c_void_p(out_off.data_ptr()), ctypes.c_void_p(docs.data_ptr()),
@@ -1592,6 +1677,47 @@ class Program:
         codec.special[:len(special)] = special
         return self._run_batch_call("run_batch_field_values_tensor", values, offsets, out, None, spec, codec)
 
+    def run_batch_field_words_tensor(self, values, offsets, ranges, quote=None, escape=None, unquote=False, special=b"\n", sep_len=0,
+                                     last_whole=False, keep_sep=True, suffix=b"", out=None):
+        """Field mode on words (kx_run_batch_field_words): run_batch_field_list_tensor where the fields of a record are the words
+        between its live blanks — spaces and tabs — as blank_field_list_records_model has them; every blank is copied as it is.
+        With `unquote` (needs a `quote` or an `escape` byte) the program runs on the VALUE of every selected word and the word is
+        replaced by the spelling of the program's output: requote_field_model with fs = the space and the 0 to 7 `special` bytes
+        plus the tab.  Returns the six tensors of run_batch_field_list_tensor; status 2 = the record has too few words,
+        fail_pos[i] of them (0 for a record without any)."""
+        what = "run_batch_field_words_tensor"
+        _check_batch_args(values, offsets)
+        ranges, sep_len = _check_field_ranges(ranges), _check_sep_len(sep_len)
+        if not isinstance(unquote, bool):
+            raise TypeError("%s: unquote must be True or False, not %s" % (what, type(unquote).__name__))
+        codec = None
+        if unquote:
+            q, e, special = _check_codec(what, quote, escape, special)
+            if len(special) > 7:
+                raise ValueError("%s: special must be 0 to 7 bytes (the tab is added), not %d" % (what, len(special)))
+            _check_not_blank(quote, escape, special=special)
+            codec = KxFieldCodec(size=ctypes.sizeof(KxFieldCodec), n_special=len(special))
+            codec.special[:len(special)] = special
+        else:
+            _check_not_blank(quote, escape)
+            q = None if quote is None else _one_byte(quote, "quote character")
+            e = None if escape is None else _one_byte(escape, "escape character")
+            if q is not None and q == e:
+                raise ValueError("escape character: %r is also the quote character" % bytes([e]))
+        for name, v in (("last_whole", last_whole), ("keep_sep", keep_sep)):
+            if not isinstance(v, bool):
+                raise TypeError("%s: %s must be True or False, not %s" % (what, name, type(v).__name__))
+        if not isinstance(suffix, (bytes, bytearray)):
+            raise TypeError("%s: suffix must be bytes of length 0 to 8, not %s" % (what, type(suffix).__name__))
+        if len(suffix) > 8:
+            raise ValueError("%s: suffix must be 0 to 8 bytes, not %d" % (what, len(suffix)))
+        arr, nr = _field_range_array(ranges)
+        spec = KxBatchFieldList(size=ctypes.sizeof(KxBatchFieldList), n_ranges=nr, ranges=arr, fs=0, quote=-1 if q is None else q,
+                                escape=-1 if e is None else e, sep_len=sep_len, last_whole=1 if last_whole else 0,
+                                keep_sep=1 if keep_sep else 0, suffix_len=len(suffix))
+        spec.suffix[:len(suffix)] = bytes(suffix)
+        return self._run_batch_call(what, values, offsets, out, None, spec, codec, words=True)
+
     def fields_kernel_stats(self):
         """kx_fields_stats: HIP-event times of field mode's own kernels, summed over this program's calls (collect_timing)."""
         st = KxFieldsKernelStats()
@@ -1651,6 +1777,25 @@ class Program:
         return field, fields
 
     @staticmethod
+    def _check_blanks(what, blanks, field, fields, fs, sep, quote, escape, rs):
+        """The `blanks=` keyword of record mode: with `field` or `fields`, without an `fs`, and with a one-byte record separator,
+        a quote and an escape byte that are no blanks → (field, fields, fs), where with `blanks` a `field=K` has become the list
+        K-K; without it `fs` has its default, a tab."""
+        if not isinstance(blanks, bool):
+            raise TypeError("%s: blanks must be True or False, not %s" % (what, type(blanks).__name__))
+        if not blanks:
+            return field, fields, b"\t" if fs is None else fs
+        if fs is not None:
+            raise ValueError("%s: blanks= cannot be combined with fs=" % what)
+        if field is None and fields is None:
+            raise ValueError("%s: blanks= needs field= or fields=" % what)
+        one = isinstance(rs, (bytes, bytearray)) and len(rs) == 1
+        _check_not_blank(quote, escape, sep if rs is None else bytes(rs) if one else None)
+        if field is not None and fields is None:
+            return None, [_check_field(field)], None
+        return field, fields, None
+
+    @staticmethod
     def _check_rs_alone(rs, sep, quote, escape, what):
         """The `rs=` keyword of record mode: 1 to 8 bytes, with the default `sep` and neither `quote` nor `escape`."""
         rs = _check_rs(rs)
@@ -1661,7 +1806,7 @@ class Program:
         return rs
 
     def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None, batch_actions=True, rs=None, chomp=False, ors=b"",
-                    field=None, fs=b"\t", fields=None, unquote=False):
+                    field=None, fs=None, fields=None, unquote=False, blanks=False):
         """Record mode on bytes: every record of `data` (split after each `sep` byte, kx_split_records on the device) is a
         whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage).  With a `quote` byte
         a separator inside quotes ends no record (kx_split_records_quoted from parity 0).  With an `escape` byte an escaped
@@ -1678,18 +1823,22 @@ class Program:
         field gives a MatchError whose `field` is the lowest rejected field and whose `pos` counts inside it.  With `unquote`
         (with `field` or `fields`, and a `quote` or an `escape`) the program runs on the VALUE of every selected field and the
         field is replaced by the spelling of its output (kx_run_batch_field_values with the separator as the special byte,
-        unquote_field_model, requote_field_model); `field=K` is then the list K-K, and `pos` counts inside the value."""
+        unquote_field_model, requote_field_model); `field=K` is then the list K-K, and `pos` counts inside the value.  With
+        `blanks` (with `field` or `fields`, not with `fs`, whose default is a tab) the fields are the words between the record's
+        live spaces and tabs and every blank is copied as it is (kx_run_batch_field_words, blank_field_list_records_model);
+        `field=K` is then the list K-K, and a record without any word gives NoFieldError(0)."""
         if not isinstance(data, (bytes, bytearray, memoryview)):
             raise TypeError("run_records: data must be bytes, not %s" % type(data).__name__)
         chomp, ors = _check_chomp(chomp), _check_ors(ors)
         field, fields = self._check_unquote("run_records", unquote, field, fields, quote, escape)
+        field, fields, fs = self._check_blanks("run_records", blanks, field, fields, fs, sep, quote, escape, rs)
         if field is not None and fields is not None:
             raise ValueError("run_records: field= and fields= exclude each other")
         if field is not None:
             field = _check_field(field)
         if fields is not None:
             fields = _check_field_ranges(fields)
-        if field is not None or fields is not None:
+        if (field is not None or fields is not None) and not blanks:
             _check_fs(fs, quote, escape, sep if rs is None else rs if len(rs) == 1 else None)
         if rs is not None:
             rs = self._check_rs_alone(rs, sep, quote, escape, "run_records")
@@ -1724,7 +1873,11 @@ class Program:
         trim = (len(rs) if rs is not None else 1) if chomp else 0
         ffield = None
         with self._batch_actions_for_call(batch_actions):
-            if unquote:
+            if blanks:
+                out, ooff, status, fpos, fstage, ffield = self.run_batch_field_words_tensor(
+                    v, offs, fields, quote, escape, unquote=unquote, special=sep_byte, sep_len=len(rs) if rs is not None else 1,
+                    last_whole=bool(tail and data), keep_sep=not chomp, suffix=ors)
+            elif unquote:
                 out, ooff, status, fpos, fstage, ffield = self.run_batch_field_values_tensor(
                     v, offs, fields, fs, quote, escape, special=sep_byte, sep_len=1, last_whole=bool(tail and data), keep_sep=not chomp,
                     suffix=ors)
@@ -1746,7 +1899,7 @@ class Program:
                 for i in range(len(status))]
 
     def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None, batch_actions=True, rs=None, chomp=False,
-                       ors=b"", field=None, fs=b"\t", fields=None, unquote=False):
+                       ors=b"", field=None, fs=None, fields=None, unquote=False, blanks=False):
         """kx_run_records_fd: the stream on in_fd in record mode, outputs to out_fd, one line per rejected record to report_fd
         (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected.  With a `quote`
         byte, kx_run_records_fd_quoted: a separator inside quotes ends no record.  With an `escape` byte,
@@ -1757,8 +1910,10 @@ class Program:
         the live `fs` bytes), the rest of the record is copied; a record with fewer fields is reported and counts as rejected.
         With `fields` (as in run_records; not with `field`), kx_run_records_fd_field_list: the program runs on every field of the
         list, and a record with a rejected field is reported once, with the field's number.  With `unquote` (as in run_records),
-        kx_run_records_fd_field_values: the program runs on the values of the selected fields, which are spelled again behind it."""
+        kx_run_records_fd_field_values: the program runs on the values of the selected fields, which are spelled again behind it.
+        With `blanks` (as in run_records), kx_run_records_fd_field_words: the fields are the words between live spaces and tabs."""
         field, fields = self._check_unquote("run_records_fd", unquote, field, fields, quote, escape)
+        field, fields, fs = self._check_blanks("run_records_fd", blanks, field, fields, fs, sep, quote, escape, rs)
         for name, fd in (("in_fd", in_fd), ("out_fd", out_fd), ("report_fd", report_fd)):
             if isinstance(fd, bool) or not isinstance(fd, int):
                 raise TypeError("run_records_fd: %s must be an int file descriptor, not %s" % (name, type(fd).__name__))
@@ -1775,7 +1930,8 @@ class Program:
             field = _check_field(field)
         if fields is not None:
             fields = _check_field_ranges(fields)
-        if field is not None or fields is not None:
+        f = 0                                            # (with blanks= there is no field separator)
+        if (field is not None or fields is not None) and not blanks:
             f = _check_fs(fs, quote, escape, sep if rs is None else rs if len(rs) == 1 else None)
         st = KxRecordsStats()
         with self._batch_actions_for_call(batch_actions):
@@ -1790,6 +1946,8 @@ class Program:
                 if fields is not None:
                     arr, nr = _field_range_array(fields)
                     name, args = "kx_run_records_fd_field_values" if unquote else "kx_run_records_fd_field_list", (ctypes.byref(o), arr, nr, f)
+                    if blanks:
+                        name, args = "kx_run_records_fd_field_words", (ctypes.byref(o), arr, nr, 1 if unquote else 0)
             else:                                        # the mode's own entry point
                 name, args = (("kx_run_records_fd", (s,)), ("kx_run_records_fd_quoted", (s, q)), ("kx_run_records_fd_escaped", (s, qi, e)),
                               ("kx_run_records_fd_rs", (rs, len(rs or b""))))[mode]
