@@ -544,6 +544,51 @@ int kx_run_batch_field_words(kx_program* prog, const void* d_in, const uint64_t*
 int kx_run_records_fd_field_words(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_field_range* ranges,
                                   uint32_t n_ranges, int unquote, int report_fd, kx_records_stats* stats);
 
+/* ---- field mode, projected: an accepted record writes the outputs of its selected fields alone, in the order the list was written ---
+ * kx_run_batch_field_project is kx_run_batch_field_list — with KX_PROJECT_WORDS kx_run_batch_field_words, with a codec
+ * kx_run_batch_field_values as well — in everything not said here; the normative text is host.project_records_model.  `proj->items`
+ * is the list AS WRITTEN: 1 to 16 items lo-hi (hi = 0: lo and every field behind it) in any order, which may overlap and repeat.
+ * The selected set S is their union, and `list` carries it and the framing: list->ranges MUST be the normal form of the items'
+ * union (kx_field_list.h has the normaliser).  `need`, the records with too few fields, "every member of S runs once, all accepted
+ * or nothing is written", d_docs, d_fail_field (the lowest rejected field NUMBER, whatever the written order), the return codes,
+ * KX_E_CAPACITY and the size query are that call's.
+ *   accepted record i: its output is, for each item in written order, the outputs of the item's fields in ascending field number
+ *     (an open item: up to the record's last field; with a codec: their spellings), every two consecutive ones joined by
+ *     ofs[0, ofs_len) + its own separator (keep_sep != 0, and the record has one) + suffix.  No byte of the body outside the
+ *     selected fields is written; a field that two items name is written twice from its one run.
+ *   With a codec the spelling protects the OUTPUT delimiter: requote_field_model's `fs` is ofs[0]; the special bytes are the
+ *     codec's (plus the tab with KX_PROJECT_WORDS).
+ * The statistics speak of the projected bytes.  KX_E_ARG besides that call's, before any device work: a null proj or a wrong
+ * `size`, 0 or more than 16 items, an item with lo = 0 or 0 < hi < lo, ofs_len > 8, unknown flag bits, a non-zero reserved word,
+ * ranges that are not the items' union; with a codec ofs_len != 1 or an OFS byte equal to the quote, the escape or a special byte.
+ * Beside that call's workspace the library holds 256 bytes for the items' table. */
+#define KX_PROJECT_WORDS 1u     /* the fields are the body's words (kx_run_batch_field_words; list->fs must be 0) */
+#define KX_PROJECT_UNQUOTE 2u   /* kx_run_records_fd_field_project only: the program runs on the fields' values */
+typedef struct kx_field_project {
+  uint32_t size;         /* sizeof(kx_field_project) */
+  uint32_t n_items;      /* 1 to 16 */
+  kx_field_range items[16];   /* as written: lo >= 1; hi == 0 (open) or hi >= lo */
+  uint32_t ofs_len;      /* 0 to 8 */
+  uint8_t ofs[8];        /* the output field separator */
+  uint32_t flags;        /* KX_PROJECT_WORDS */
+  uint32_t reserved[4];  /* must be 0 */
+} kx_field_project;
+int kx_run_batch_field_project(kx_program* prog, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* list,
+                               const kx_field_codec* codec /* or NULL */, const kx_field_project* proj, void* d_out, size_t cap,
+                               uint64_t* d_out_off, kx_batch_doc* d_docs, uint32_t* d_fail_field, size_t* out_len, kx_batch_stats* stats,
+                               void* stream);
+
+/* kx_run_records_fd_field_list, projected (`BIN --records … --field=K|LIST [--fs=F | --blanks] [--unquote] --only [--ofs=STR]`): every
+ * record goes through kx_run_batch_field_project with items[0, n_items) as written, the normal form of their union for the list
+ * and ofs[0, ofs_len).  flags: KX_PROJECT_WORDS (the fields are words; `fs` is not used) and KX_PROJECT_UNQUOTE (with a codec whose
+ * special byte is o->sep).  The report lines are kx_run_records_fd_field_list's.  KX_E_ARG: the rules of the entry point the flags
+ * name (kx_run_records_fd_field_list, _field_values, _field_words), invalid items or more than 16, a union of more than 8 ranges,
+ * ofs_len > 8, unknown flag bits, and with KX_PROJECT_UNQUOTE an OFS that is not one byte or equals the quote, the escape or the
+ * record separator. */
+int kx_run_records_fd_field_project(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_field_range* items,
+                                    uint32_t n_items, uint8_t fs, const uint8_t* ofs, uint32_t ofs_len, uint32_t flags, int report_fd,
+                                    kx_records_stats* stats);
+
 /* ---- sharded execution: one contiguous shard of the input per GPU -------------
  * Per stage and per rank:
  *   kx_shard_begin → kx_shard_forward → [exchange kx_fwd_summary] → kx_shard_fix_head

@@ -23,7 +23,8 @@
 // Bytes are read only inside a record's own range (k_flcount, k_fllocate: inside the granules of its body), written only below the
 // total; every output byte is written exactly once.
 
-constexpr unsigned long long FL_OPEN = ~0ull;      // hi of an open range; lo and hi of the entries behind the list's last range
+// (FL_OPEN, hi of an open range and lo and hi of the entries behind the list's last range, is kx_field_lanes.h's, with fl_member,
+// fl_missing and fl_status, which walk the table)
 
 // what the kernels know of a kx_batch_field_list (F.field is not used).  The ranges are a table in device memory, lo[0..7] then
 // hi[0..7]: a kernel argument indexed by the cursor would go through scratch, and 32 more SGPRs would not fit.
@@ -150,26 +151,6 @@ __global__ __launch_bounds__(FLD_BT) void k_fllocate(const uint8_t* __restrict__
   }
 }
 
-// field number of the list's member number t (from 0)
-__device__ __forceinline__ unsigned long long fl_member(const FLSpec& L, unsigned long long t) {
-  for (uint32_t k = 0; k < 8; ++k) {
-    const unsigned long long lo = L.rng[k], hi = L.rng[8 + k];
-    const unsigned long long size = hi == FL_OPEN ? FL_OPEN : hi - lo + 1;   // (behind the list: FL_OPEN, never reached)
-    if (t < size) return lo + t;
-    t -= size;
-  }
-  return 0;
-}
-
-// the smallest member of the list above `fields` (there is one: fields < need)
-__device__ __forceinline__ unsigned long long fl_missing(const FLSpec& L, unsigned long long fields) {
-  for (uint32_t k = 0; k < 8; ++k) {
-    const unsigned long long lo = L.rng[k], hi = L.rng[8 + k];
-    if (lo != FL_OPEN && hi > fields) return lo > fields ? lo : fields + 1;
-  }
-  return 0;
-}
-
 __global__ __launch_bounds__(FLD_BT) void k_flsplen(const unsigned long long* __restrict__ off, unsigned long long n, FLSpec L,
                                                     const unsigned long long* __restrict__ d0, const unsigned long long* __restrict__ nf,
                                                     const unsigned long long* __restrict__ coff, const unsigned long long* __restrict__ poff,
@@ -183,14 +164,8 @@ __global__ __launch_bounds__(FLD_BT) void k_flsplen(const unsigned long long* __
     if (i < n) {
       BDoc d{0, 0, BM_RUN, 0};
       const unsigned long long da = d0[i], db = d0[i + 1];
-      kx_batch_doc r{0, 0u, 0u};
-      unsigned long long K = 0;
-      if (da == db) { r = kx_batch_doc{nf[i], 2u, 0u}; K = fl_missing(L, nf[i]); }
-      else {
-        unsigned long long t = da;
-        while (t < db && drec[t].status == 0) ++t;              // the lowest rejected field
-        if (t < db) { r = drec[t]; K = fl_member(L, t - da); }
-      }
+      unsigned long long K;
+      const kx_batch_doc r = fl_status(L.rng, i, da, db, nf, drec, K);
       rejected = r.status != 0;
       if (!rejected) {
         const unsigned long long s = off[i], e = off[i + 1], be = fld_body_end(e, i, L.F);
@@ -282,13 +257,13 @@ __global__ __launch_bounds__(FLD_GT) void k_flsplice(const uint8_t* __restrict__
 // length record (the document count, then the output length), 8 of the first document's index, 8 of the fields found.  Per
 // document (selected field): 8 + 8 bytes of field bounds, 16 of a length record, 8 + 8 of the two offset arrays, 16 of the inner
 // batch's document record.  Per selected byte one of the compact buffer; per byte of program output one of the second buffer.  128
-// bytes for the ranges' table.
+// bytes for the ranges' table; with a projection (kx_field_project.inc) 256 for the items'.
 struct FieldListWs {
-  BatchWs::Buf ctr, rng, cnt, d0, nf, fb, fe, len, coff, comp, pout, poff, drec, wsum, woff, flags;
+  BatchWs::Buf ctr, rng, itm, cnt, d0, nf, fb, fe, len, coff, comp, pout, poff, drec, wsum, woff, flags;
   hipEvent_t ev[12] = {};
   bool have_events = false;
   ~FieldListWs() {
-    for (BatchWs::Buf* b : {&ctr, &rng, &cnt, &d0, &nf, &fb, &fe, &len, &coff, &comp, &pout, &poff, &drec, &wsum, &woff, &flags}) if (b->p) (void)hipFree(b->p);
+    for (BatchWs::Buf* b : {&ctr, &rng, &itm, &cnt, &d0, &nf, &fb, &fe, &len, &coff, &comp, &pout, &poff, &drec, &wsum, &woff, &flags}) if (b->p) (void)hipFree(b->p);
     if (have_events) for (auto& e : ev) (void)hipEventDestroy(e);
   }
 };

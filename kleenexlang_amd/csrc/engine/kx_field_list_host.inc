@@ -34,10 +34,14 @@ int checkFieldList(const kx_batch_field_list& l, const char* who) {
 // before k_flsplen and k_flsplice, which then take the spellings and their offsets for the outputs and theirs (kx_field_values.inc).
 // Without one, the kernels and their arguments are the list's own.  With `words` (kx_run_batch_field_words, kx_field_words_host.inc)
 // the fields are the body's words: k_fwcount and k_fwlocate (kx_field_words.inc) take the place of k_flcount and k_fllocate, l->fs
-// is not used, and the value kernels' field separator is the space.  Nothing else differs.
+// is not used, and the value kernels' field separator is the space.  Nothing else differs.  With `proj`
+// (kx_run_batch_field_project, kx_field_project_host.inc, whose checks have passed) steps 1 to 4v are the same but for the value
+// kernels' field separator, which is the OFS byte, and steps 5 and 6 are k_fpsplen and k_fpsplice (kx_field_project.inc) over the
+// items' table; without it every launch and every argument is what it is without the parameter.
 int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* l,
                  const kx_field_codec* codec, void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs, uint32_t* d_fail_field,
-                 size_t* out_len, kx_batch_stats* stats, void* stream, const char* who, bool words = false) {
+                 size_t* out_len, kx_batch_stats* stats, void* stream, const char* who, bool words = false,
+                 const kx_field_project* proj = nullptr) {
   if (n_docs && (!d_in_off || !d_out_off || !d_docs)) return setErr(KX_E_ARG, std::string(who) + ": offsets, output offsets and document records are required");
   if (n_docs >= 0xFFFFFFFFull) return setErr(KX_E_ARG, std::string(who) + ": at most 2^32 - 2 documents per call");
   *out_len = 0;
@@ -64,6 +68,7 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
   const uint64_t nd = n_docs;
   int rc = BatchWs::ensure(W.ctr, FC_N * 8);
   if (!rc) rc = BatchWs::ensure(W.rng, 16 * 8);
+  if (!rc && proj) rc = BatchWs::ensure(W.itm, 32 * 8);
   if (!rc) rc = BatchWs::ensure(W.d0, (nd + 1) * 8);
   if (!rc) rc = BatchWs::ensure(W.nf, nd * 8);
   if (!rc) rc = BatchWs::ensure(W.cnt, nd * sizeof(BDoc));
@@ -90,9 +95,26 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
   }
   unsigned long long sfx8 = 0;
   for (uint32_t i = 0; i < l->suffix_len; ++i) sfx8 |= (unsigned long long)l->suffix[i] << (8 * i);
+  FPSpec P{};                    // with a projection: the items' table rank[0..15], size[0..15], and the framing once more
+  unsigned long long hitm[32];
+  if (proj) {
+    P = FPSpec{L.rng, (const unsigned long long*)W.itm.p, L.F.sep_len, L.F.whole, 0ull, sfx8, proj->n_items, proj->ofs_len, l->suffix_len, L.F.keep};
+    for (uint32_t i = 0; i < proj->ofs_len; ++i) P.ofs8 |= (unsigned long long)proj->ofs[i] << (8 * i);
+    for (uint32_t j = 0; j < 16; ++j) {
+      const bool in = j < proj->n_items;
+      unsigned long long rk = 0;   // the members of S below the item's lo: the ranges in front of the one that holds it, and its part of that
+      for (uint32_t k = 0; in && k < l->n_ranges && l->ranges[k].lo <= proj->items[j].lo; ++k) {
+        const bool holds = l->ranges[k].hi == 0 || l->ranges[k].hi >= proj->items[j].lo;
+        rk += (unsigned long long)(holds ? proj->items[j].lo : l->ranges[k].hi + 1ull) - l->ranges[k].lo;
+      }
+      hitm[j] = rk;
+      hitm[16 + j] = !in ? 0ull : proj->items[j].hi ? (unsigned long long)proj->items[j].hi - proj->items[j].lo + 1 : FL_OPEN;
+    }
+  }
   // the offsets, checked on the device before any kernel reads a record
   HIPCHECK(hipMemsetAsync(ctr, 0, FC_N * 8, sm));
   HIPCHECK(hipMemcpyAsync(W.rng.p, hrng, sizeof hrng, hipMemcpyHostToDevice, sm));   // (hrng lives until the sync below)
+  if (proj) HIPCHECK(hipMemcpyAsync(W.itm.p, hitm, sizeof hitm, hipMemcpyHostToDevice, sm));   // (and hitm)
   hipLaunchKernelGGL(k_fcheck, dim3((uint32_t)((nd + 255) / 256)), dim3(256), 0, sm, off, (unsigned long long)nd, L.F, ctr);
   HIPCHECK(hipGetLastError());
   unsigned long long hc[FC_N] = {}, ends[2] = {0, 0};
@@ -149,7 +171,7 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
     FVSpec C{};           // with a codec only: the bytes of the value kernels, and their grid (lane = document)
     uint32_t dgrid = 0;
     if (V) {
-      C = FVSpec{words ? 0x20u : (uint32_t)l->fs, L.F.quote, L.F.escape, codec->n_special, 0ull};
+      C = FVSpec{proj ? (uint32_t)proj->ofs[0] : words ? 0x20u : (uint32_t)l->fs, L.F.quote, L.F.escape, codec->n_special, 0ull};
       for (uint32_t i = 0; i < C.nsp; ++i) C.sp8 |= (unsigned long long)codec->special[i] << (8 * i);
       dgrid = (uint32_t)std::min<uint64_t>((ndocs + FLD_BT - 1) / FLD_BT, (uint64_t)p->ncu * 4);
     }
@@ -234,9 +256,13 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
   // 5. the records' results and output lengths, and their scan into the caller's offsets
   BDoc* rlen = cnt;   // (the counts have been scanned into d0)
   if (timing) HIPCHECK(hipEventRecord(W.ev[8], sm));
-  hipLaunchKernelGGL(k_flsplen, dim3(bgrid), dim3(FLD_BT), 0, sm, off, (unsigned long long)nd, L, (const unsigned long long*)d0,
-                     (const unsigned long long*)nf, (const unsigned long long*)coff, (const unsigned long long*)poff, (const kx_batch_doc*)drec,
-                     d_docs, d_fail_field, (unsigned long long)l->suffix_len, rlen, ctr);
+  if (proj)
+    hipLaunchKernelGGL(k_fpsplen, dim3(bgrid), dim3(FLD_BT), 0, sm, off, (unsigned long long)nd, P, (const unsigned long long*)d0,
+                       (const unsigned long long*)nf, (const unsigned long long*)poff, (const kx_batch_doc*)drec, d_docs, d_fail_field, rlen, ctr);
+  else
+    hipLaunchKernelGGL(k_flsplen, dim3(bgrid), dim3(FLD_BT), 0, sm, off, (unsigned long long)nd, L, (const unsigned long long*)d0,
+                       (const unsigned long long*)nf, (const unsigned long long*)coff, (const unsigned long long*)poff, (const kx_batch_doc*)drec,
+                       d_docs, d_fail_field, (unsigned long long)l->suffix_len, rlen, ctr);
   scanLens(rlen, nd, (unsigned long long*)d_out_off);
   if (timing) HIPCHECK(hipEventRecord(W.ev[9], sm));
   HIPCHECK(hipGetLastError());
@@ -253,7 +279,11 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
   if (total > cap || (total && !d_out)) return setErr(KX_E_CAPACITY, "output buffer too small");
   // 6. the splice
   if (timing) HIPCHECK(hipEventRecord(W.ev[10], sm));
-  if (total)
+  if (total && proj)
+    hipLaunchKernelGGL(k_fpsplice, granGrid(total), dim3(FLD_GT), 0, sm, in, off, (unsigned long long)nd, P, (const unsigned long long*)d0,
+                       spliced ? spliced : (const uint8_t*)W.pout.p, (const unsigned long long*)poff, (const unsigned long long*)d_out_off, total,
+                       (uint8_t*)d_out);
+  else if (total)
     hipLaunchKernelGGL(k_flsplice, granGrid(total), dim3(FLD_GT), 0, sm, in, off, (unsigned long long)nd, L.F, (const unsigned long long*)d0,
                        (const unsigned long long*)fb, (const unsigned long long*)fe, (const unsigned long long*)coff,
                        spliced ? spliced : (const uint8_t*)W.pout.p, (const unsigned long long*)poff, (const unsigned long long*)d_out_off, total, sfx8, (uint8_t*)d_out);

@@ -25,6 +25,8 @@
 //               byte stores in the two partial ones.  Every output byte is written exactly once.
 // Bytes are read only inside a record's own range (k_flocate: inside the granules of its body), written only below the total.
 
+#include "kx_field_lanes.h"   // fld_find, fld_put: the splice kernels' helpers, which also compile as plain C++
+
 constexpr uint32_t FLD_BT = 512;                   // threads per workgroup of the per-record kernels
 constexpr uint32_t FLD_GT = 256;                   // threads per workgroup of the per-granule kernels
 constexpr unsigned long long FLD_NONE = ~0ull;     // fb[i]: the record has no field K (fe[i] = the fields it has)
@@ -120,20 +122,6 @@ __global__ __launch_bounds__(FLD_BT) void k_flocate(const uint8_t* __restrict__ 
     }
     len[i] = d;
   }
-}
-
-// the last index r with o[r] <= pos, for pos < o[n] (o: n + 1 non-decreasing entries, o[0] = 0)
-__device__ __forceinline__ unsigned long long fld_find(const unsigned long long* __restrict__ o, unsigned long long n, unsigned long long pos) {
-  unsigned long long lo = 0, hi = n + 1;
-  while (lo < hi) {
-    const unsigned long long mid = (lo + hi) >> 1;
-    if (o[mid] <= pos) lo = mid + 1; else hi = mid;
-  }
-  return lo - 1;
-}
-
-__device__ __forceinline__ void fld_put(unsigned long long& lo, unsigned long long& hi, uint32_t k, uint8_t v) {
-  if (k < 8) lo |= (unsigned long long)v << (8 * k); else hi |= (unsigned long long)v << (8 * (k - 8));
 }
 
 // comp (16-byte aligned, room for the last granule) = the fields one after the other; coff: their scanned lengths

@@ -27,7 +27,9 @@
 // fields (kx_run_records_fd_field_list) it calls kx_run_batch_field_list the same way; the report lines name the field.  On unquoted
 // values (kx_run_records_fd_field_values) it calls kx_run_batch_field_values with the list and a codec whose one special byte is the
 // record separator.  On words (kx_run_records_fd_field_words) it calls kx_run_batch_field_words with the list, fs = 0 and, with
-// `unquote`, that codec; checkRecordsOpts has the blank rules.
+// `unquote`, that codec; checkRecordsOpts has the blank rules.  Projected (kx_run_records_fd_field_project) RecordsRun holds the
+// kx_field_project beside the ranges, which are the normal form of its items' union, and calls kx_run_batch_field_project for the
+// carried record and the window's records alike, with the codec and the words flag as above.
 
 namespace {
 
@@ -244,6 +246,7 @@ struct RecordsRun {
   uint32_t n_ranges = 0;                               //   (0: no list; `field` is 0 with a list)
   kx_field_codec codec{};                              // ... on their values (size != 0: kx_run_batch_field_values; special = the separator)
   bool words = false;                                  // ... which are the body's words (kx_run_batch_field_words; fsep is not used)
+  kx_field_project proj{};                             // ... projected (size != 0: kx_run_batch_field_project; ranges = the items' union)
   SplitCarry next;                                     // what the next window's split starts from
   int report_fd = -1;
   RecWs ws;
@@ -306,6 +309,9 @@ struct RecordsRun {
     ll.suffix_len = fl.suffix_len;
     memcpy(ll.suffix, fl.suffix, sizeof ll.suffix);
     auto run = [&](void* d_out, size_t cap, size_t* ol, kx_batch_stats* bs) {
+      if (n_ranges && proj.size)
+        return kx_run_batch_field_project(p, in, d_o, ndocs, &ll, codec.size ? &codec : nullptr, &proj, d_out, cap, (uint64_t*)ooff.p,
+                                          (kx_batch_doc*)docs.p, (uint32_t*)ffield.p, ol, bs, nullptr);
       if (n_ranges && words)
         return kx_run_batch_field_words(p, in, d_o, ndocs, &ll, codec.size ? &codec : nullptr, d_out, cap, (uint64_t*)ooff.p, (kx_batch_doc*)docs.p,
                                         (uint32_t*)ffield.p, ol, bs, nullptr);
@@ -558,7 +564,8 @@ int checkRecordsOpts(const kx_records_opts& o, const char* who, int fs = -1, boo
 
 // the stream on in_fd in record mode as `o` says (checkRecordsOpts has passed)
 int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o, int report_fd, kx_records_stats* stats, uint32_t field = 0,
-                 uint8_t fsep = 0, const kx_field_range* ranges = nullptr, uint32_t n_ranges = 0, bool values = false, bool words = false) {
+                 uint8_t fsep = 0, const kx_field_range* ranges = nullptr, uint32_t n_ranges = 0, bool values = false, bool words = false,
+                 const kx_field_project* proj = nullptr) {
   if (!p) return setErr(KX_E_ARG, "null argument");
   if (p->cfg.phase) return setErr(KX_E_ARG, "record mode runs every phase: kx_config::phase must be 0");
   const double t_begin = FdStream::nowMs();
@@ -574,6 +581,7 @@ int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o,
   R.p = p; R.fs = &fsr; R.o = o; R.report_fd = report_fd; R.field = field; R.fsep = fsep;
   R.n_ranges = n_ranges; R.words = words;
   if (n_ranges) memcpy(R.ranges, ranges, n_ranges * sizeof(kx_field_range));
+  if (proj) R.proj = *proj;
   if (values) { R.codec.size = sizeof R.codec; R.codec.n_special = 1; R.codec.special[0] = o.sep; }
   R.timing = p->cfg.collect_timing != 0;
   int rc = 0;
@@ -663,4 +671,33 @@ extern "C" int kx_run_records_fd_field_words(kx_program* p, int in_fd, int out_f
   if (const int rc = checkRecordsOpts(*o, who, -1, true)) return rc;
   if (unquote && o->mode != KX_RECORDS_QUOTED && o->mode != KX_RECORDS_ESCAPED) return setErr(KX_E_ARG, std::string(who) + ": values need a quote or an escape byte");
   return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, 0, 0, ranges, n_ranges, unquote != 0, true);
+}
+
+extern "C" int kx_run_records_fd_field_project(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_field_range* items,
+                                               uint32_t n_items, uint8_t fs, const uint8_t* ofs, uint32_t ofs_len, uint32_t flags, int report_fd,
+                                               kx_records_stats* stats) {
+  static const char* const who = "kx_run_records_fd_field_project";
+  auto no = [&](const char* what) { return setErr(KX_E_ARG, std::string(who) + ": " + what); };
+  if (!o || !items || (ofs_len && !ofs)) return setErr(KX_E_ARG, "null argument");
+  if (flags & ~(KX_PROJECT_WORDS | KX_PROJECT_UNQUOTE)) return no("unknown flag bits");
+  if (!kxFieldItemsAreValid(items, n_items)) return no("the list as written has 1 to 16 items, each with lo >= 1 and hi = 0 (open) or hi >= lo");
+  if (ofs_len > 8) return no("the output field separator is at most 8 bytes");
+  kx_field_range ranges[KX_FIELD_RANGES] = {};
+  uint32_t n_ranges = 0;
+  if (kxFieldItemsUnion(items, n_items, ranges, &n_ranges)) return no("the items' union has more than 8 ranges in its normal form");
+  const bool words = (flags & KX_PROJECT_WORDS) != 0, unquote = (flags & KX_PROJECT_UNQUOTE) != 0;
+  if (const int rc = words ? checkRecordsOpts(*o, who, -1, true) : checkRecordsOpts(*o, who, fs)) return rc;
+  if (unquote) {
+    if (o->mode != KX_RECORDS_QUOTED && o->mode != KX_RECORDS_ESCAPED) return no("values need a quote or an escape byte");
+    if (ofs_len != 1) return no("on values the output field separator is exactly one byte");
+    if (ofs[0] == o->sep) return no("the output field separator cannot be the record separator");
+    if ((int)ofs[0] == o->quote) return no("the output field separator cannot be the quote byte");
+    if (o->mode == KX_RECORDS_ESCAPED && (int)ofs[0] == o->escape) return no("the output field separator cannot be the escape byte");
+    if (words && ofs[0] == 0x09) return no("on the values of words the output field separator cannot be the tab");
+  }
+  kx_field_project pr{};
+  pr.size = sizeof pr; pr.n_items = n_items; pr.ofs_len = ofs_len; pr.flags = words ? KX_PROJECT_WORDS : 0u;
+  memcpy(pr.items, items, n_items * sizeof(kx_field_range));
+  if (ofs_len) memcpy(pr.ofs, ofs, ofs_len);
+  return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, 0, words ? (uint8_t)0 : fs, ranges, n_ranges, unquote, words, &pr);
 }

@@ -25,8 +25,11 @@
 // --quote or --escape) the program runs on the VALUE of each selected field, and the field is replaced by the spelling of its
 // output, quoted and escaped as it needs (kx_run_records_fd_field_values; --field=K is then the list K-K).  With `--blanks` (with
 // --field, not with --fs) the fields are the words between runs of live spaces and tabs, as awk's default splitting has them, and
-// every blank is copied as it is (kx_run_records_fd_field_words; --field=K is then the list K-K, with or without --unquote).  What
-// --field, --fs, --unquote and --blanks refuse exits with status 2.
+// every blank is copied as it is (kx_run_records_fd_field_words; --field=K is then the list K-K, with or without --unquote).  With
+// `--only` (with --field) an accepted record writes the outputs of the selected fields alone, in the order the list was WRITTEN
+// (up to 16 items, which may overlap and repeat) and joined by the 0 to 8 bytes of `--ofs=STR` (spelled as --ors; default the --fs
+// byte, or one space with --blanks), then separator and --ors as ever (kx_run_records_fd_field_project; kxParseFieldOrder).  What
+// --field, --fs, --unquote, --blanks, --only and --ofs refuse exits with status 2.
 //
 // BIN = this executable ++ KXP blob ++ libdir ++ trailer (see kexc main.cpp).
 // The engine is loaded with dlopen so that this file carries no HIP dependency.
@@ -94,6 +97,7 @@ static void usage(const char* name) {
   fprintf(stdout, "- \"%s --records ... --field=LIST [--fs=F]\": the same on every field of LIST (2,5-7,9-); a record is written only if all of them are accepted.\n", name);
   fprintf(stdout, "- \"%s --records ... --quote|--escape --field=K|LIST [--fs=F] --unquote\": the program runs on the unquoted value of every selected field; its output is quoted again as it needs.\n", name);
   fprintf(stdout, "- \"%s --records ... --field=K|LIST --blanks [--unquote]\": the fields are the words between runs of spaces and tabs (awk's default); every blank is copied as it is.\n", name);
+  fprintf(stdout, "- \"%s --records ... --field=K|LIST [--fs=F | --blanks] [--unquote] --only [--ofs=STR]\": writes only the selected fields' outputs, in the order LIST is written (4,2 or 2,1,2), joined by STR (0 to 8 bytes; default F, or a space with --blanks).\n", name);
 }
 
 // --records=SEP, --quote=Q, --escape=E: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
@@ -179,7 +183,8 @@ int main(int argc, char** argv) {
                                          {"escape", optional_argument, 0, 'e'}, {"rs", required_argument, 0, 's'},
                                          {"chomp", no_argument, 0, 'c'}, {"ors", required_argument, 0, 'o'},
                                          {"field", required_argument, 0, 'f'}, {"fs", required_argument, 0, 'F'},
-                                         {"unquote", no_argument, 0, 'u'}, {"blanks", no_argument, 0, 'b'}, {0, 0, 0, 0}};
+                                         {"unquote", no_argument, 0, 'u'}, {"blanks", no_argument, 0, 'b'},
+                                         {"only", no_argument, 0, 'y'}, {"ofs", required_argument, 0, 'O'}, {0, 0, 0, 0}};
   bool timing = false, records = false, quoted = false, escaped = false, sep_given = false, multi = false, chomp = false, ors_given = false;
   uint8_t sep = '\n', quote = '"', escape = '\\', rs[8] = {}, ors[8] = {};
   uint32_t rs_len = 0, ors_len = 0, field = 0;
@@ -187,6 +192,11 @@ int main(int argc, char** argv) {
   kx_field_range ranges[KX_FIELD_RANGES] = {};   // --field=LIST in normal form (n_ranges = 0: --field=K, one plain number)
   uint32_t n_ranges = 0;
   uint8_t fsep = '\t';
+  bool only = false, ofs_given = false;
+  const char* field_text = nullptr;              // --field's text: with --only it is parsed once more, as written
+  kx_field_range items[KX_FIELD_ITEMS] = {};     // --only: the list as written
+  uint32_t n_items = 0, ofs_len = 0;
+  uint8_t ofs[8] = {};
   long phase = 0, gpus = 0;
   int c;
   while ((c = getopt_long(argc, argv, "ihtp:", long_options, nullptr)) != -1) {
@@ -226,6 +236,7 @@ int main(int argc, char** argv) {
         break;
       case 'f': {
         field_given = true;
+        field_text = optarg;
         n_ranges = 0; field = 0;
         if (strpbrk(optarg, ",-")) {   // a list; one plain number (and what is neither) takes the single-field path below
           if (const char* why = kxParseFieldList(optarg, ranges, &n_ranges)) {
@@ -246,6 +257,11 @@ int main(int argc, char** argv) {
         break;
       case 'u': unquote = true; break;
       case 'b': blanks = true; break;
+      case 'y': only = true; break;
+      case 'O':
+        ofs_given = true;
+        if (!parseOutputSeparator(optarg, ofs, &ofs_len)) { fprintf(stderr, "Invalid output field separator: %s\n", optarg); return 2; }
+        break;
       case 'h':
       default: usage(argv[0]); return 1;
     }
@@ -276,6 +292,20 @@ int main(int argc, char** argv) {
   if (field_given && escaped && fsep == escape) { fprintf(stderr, "%s: --fs cannot be the --escape character\n", argv[0]); return 2; }
   if (unquote && !field_given) { fprintf(stderr, "%s: --unquote needs --field\n", argv[0]); return 2; }
   if (unquote && !quoted && !escaped) { fprintf(stderr, "%s: --unquote needs --quote or --escape\n", argv[0]); return 2; }
+  if (only && !field_given) { fprintf(stderr, "%s: --only needs --field\n", argv[0]); return 2; }
+  if (ofs_given && !only) { fprintf(stderr, "%s: --ofs needs --only\n", argv[0]); return 2; }
+  if (only) {   // the list as written (a plain number is the list K-K); its union is what the list's own parse gave
+    if (const char* why = kxParseFieldOrder(field_text, items, &n_items, ranges, &n_ranges)) {
+      fprintf(stderr, "Invalid --field: %s (with --only a list of at most 16 items such as 4,2 or 2,1,2: %s)\n", field_text, why);
+      return 2;
+    }
+    if (!ofs_given) { ofs[0] = blanks ? (uint8_t)' ' : fsep; ofs_len = 1; }
+    if (unquote && ofs_len != 1) { fprintf(stderr, "%s: with --unquote --ofs is exactly one byte\n", argv[0]); return 2; }
+    if (unquote && quoted && ofs[0] == quote) { fprintf(stderr, "%s: with --unquote --ofs cannot be the --quote character\n", argv[0]); return 2; }
+    if (unquote && escaped && ofs[0] == escape) { fprintf(stderr, "%s: with --unquote --ofs cannot be the --escape character\n", argv[0]); return 2; }
+    if (unquote && (multi ? rs_len == 1 && ofs[0] == rs[0] : ofs[0] == sep)) { fprintf(stderr, "%s: with --unquote --ofs cannot be the record separator\n", argv[0]); return 2; }
+    if (unquote && blanks && ofs[0] == '\t') { fprintf(stderr, "%s: with --unquote and --blanks --ofs cannot be the tab\n", argv[0]); return 2; }
+  }
   if ((unquote || blanks) && !n_ranges) { ranges[0] = kx_field_range{field, field}; n_ranges = 1; }   // --field=K on values or words: the list K-K
   struct timeval t0, t1;
   if (timing) gettimeofday(&t0, nullptr);
@@ -301,14 +331,16 @@ int main(int argc, char** argv) {
     decltype(&kx_run_records_fd_fields) runf = nullptr;
     decltype(&kx_run_records_fd_field_list) runl = nullptr;
     decltype(&kx_run_records_fd_field_words) runw = nullptr;
+    decltype(&kx_run_records_fd_field_project) runp = nullptr;
     if (!runr) return 1;
     if (quoted && !(runq = (decltype(runq))engineSymbol(h, argv[0], "kx_run_records_fd_quoted", "--quote needs"))) return 1;
     if (escaped && !(rune = (decltype(rune))engineSymbol(h, argv[0], "kx_run_records_fd_escaped", "--escape needs"))) return 1;
     if (multi && !(runm = (decltype(runm))engineSymbol(h, argv[0], "kx_run_records_fd_rs", "--rs needs"))) return 1;
+    if (only && !(runp = (decltype(runp))engineSymbol(h, argv[0], "kx_run_records_fd_field_project", "--only needs"))) return 1;
     if (field_given && !n_ranges && !(runf = (decltype(runf))engineSymbol(h, argv[0], "kx_run_records_fd_fields", "--field needs"))) return 1;
-    if (blanks && !(runw = (decltype(runw))engineSymbol(h, argv[0], "kx_run_records_fd_field_words", "--blanks needs"))) return 1;
-    if (n_ranges && !unquote && !blanks && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_list", "--field=LIST needs"))) return 1;
-    if (unquote && !blanks && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_values", "--unquote needs"))) return 1;   // (the same signature)
+    if (blanks && !only && !(runw = (decltype(runw))engineSymbol(h, argv[0], "kx_run_records_fd_field_words", "--blanks needs"))) return 1;
+    if (n_ranges && !unquote && !blanks && !only && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_list", "--field=LIST needs"))) return 1;
+    if (unquote && !blanks && !only && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_values", "--unquote needs"))) return 1;   // (the same signature)
     if (framing && !(runo = (decltype(runo))engineSymbol(h, argv[0], "kx_run_records_fd_opts", "--chomp and --ors need"))) return 1;
     // record mode is where the single-document route is unusable (a third of a millisecond per record): stages with register
     // actions are replayed by the batch kernels unless KX_BATCH_ACTIONS=0 asks for the route
@@ -326,7 +358,9 @@ int main(int argc, char** argv) {
       memcpy(o.rs, rs, 8); o.rs_len = rs_len;
       o.chomp = chomp ? 1u : 0u;
       memcpy(o.ors, ors, 8); o.ors_len = ors_len;
-      rc = blanks      ? runw(prog, STDIN_FILENO, STDOUT_FILENO, &o, ranges, n_ranges, unquote ? 1 : 0, STDERR_FILENO, &rs_stats)
+      rc = only        ? runp(prog, STDIN_FILENO, STDOUT_FILENO, &o, items, n_items, fsep, ofs, ofs_len,
+                                (blanks ? KX_PROJECT_WORDS : 0u) | (unquote ? KX_PROJECT_UNQUOTE : 0u), STDERR_FILENO, &rs_stats)
+           : blanks    ? runw(prog, STDIN_FILENO, STDOUT_FILENO, &o, ranges, n_ranges, unquote ? 1 : 0, STDERR_FILENO, &rs_stats)
            : n_ranges  ? runl(prog, STDIN_FILENO, STDOUT_FILENO, &o, ranges, n_ranges, fsep, STDERR_FILENO, &rs_stats)
            : field_given ? runf(prog, STDIN_FILENO, STDOUT_FILENO, &o, field, fsep, STDERR_FILENO, &rs_stats)
                        : runo(prog, STDIN_FILENO, STDOUT_FILENO, &o, STDERR_FILENO, &rs_stats);

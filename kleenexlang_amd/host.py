@@ -744,6 +744,94 @@ def blank_field_list_records_model(data, offsets, sep_len, last_whole, ranges, q
     return res
 
 
+FIELD_ITEMS_MAX = 16
+
+
+def parse_field_order(text):
+    """The LIST of `--field=LIST --only` AS WRITTEN → a tuple of (lo, hi) pairs with hi None for an open item, in the order of the
+    text: the order of the output.  The number rules are parse_field_list's; items may come in any order, overlap and repeat
+    ("2,1,2", "3-,1-2").  Raises ValueError for what the command line refuses: what parse_field_list refuses (the normal form of
+    the items' union has at most 8 ranges), and more than 16 items."""
+    parse_field_list(text)                                      # (every rule of the text but the number of items)
+    items = []
+    for item in text.split(","):
+        a, dash, b = item.partition("-")
+        items.append((int(a), int(a) if not dash else None if not b else int(b)))
+    if len(items) > FIELD_ITEMS_MAX:
+        raise ValueError("field list %r: %d items, at most %d with only=" % (text, len(items), FIELD_ITEMS_MAX))
+    return tuple(items)
+
+
+def _check_field_items(items):
+    """The `items` of a projection: a parse_field_order result, or a sequence of 1 to 16 field numbers and (lo, hi) pairs (hi
+    None: open), in any order → (the items as written, a tuple of pairs; the normal form of their union)."""
+    ranges = _check_field_ranges(items)                         # (the types, the numbers and the union's 8 ranges)
+    if len(items) > FIELD_ITEMS_MAX:
+        raise ValueError("fields: %d items, at most %d with only=" % (len(items), FIELD_ITEMS_MAX))
+    return tuple((it[0], it[1]) if isinstance(it, (tuple, list)) else (it, it) for it in items), ranges
+
+
+def project_records_model(data, offsets, sep_len, last_whole, items, fs, quote=None, escape=None, blanks=False):
+    """kx_run_batch_field_project's view of its records in pure Python — the normative model of `--field=LIST --only`.  `items` is
+    the list as written (what parse_field_order gives, or a sequence of ints and (lo, hi) pairs).  The selected set is the items'
+    union, and everything about it is field_list_records_model's — with `blanks` (and fs None) blank_field_list_records_model's —
+    for the union's normal form: a record with fewer than `need` fields gives the number of fields it has.  Any other record
+    gives ([(K, field bytes), …], separator): for each item in written order the item's fields in ascending field number, an open
+    item up to the record's last field.  A field that two items name comes twice; an item none of whose fields the record has (it
+    lies inside the union's open range: "3-,9-10" on five fields) gives none.  The list is never empty."""
+    if not isinstance(blanks, bool):
+        raise TypeError("project_records_model: blanks must be True or False, not %s" % type(blanks).__name__)
+    items, ranges = _check_field_items(items)
+    if blanks:
+        if fs is not None:
+            raise ValueError("project_records_model: blanks= cannot be combined with an fs")
+        recs = blank_field_list_records_model(data, offsets, sep_len, last_whole, ranges, quote, escape)
+    else:
+        recs = field_list_records_model(data, offsets, sep_len, last_whole, ranges, fs, quote, escape)
+    res = []
+    for r in recs:
+        if isinstance(r, int):
+            res.append(r)
+            continue
+        _, fields, sep = r
+        res.append(([(K, v) for lo, hi in items for K, v in fields if lo <= K and (hi is None or K <= hi)], sep))
+    return res
+
+
+class KxFieldProject(ctypes.Structure):
+    """include/kxhip.h::kx_field_project."""
+    _fields_ = [("size", ctypes.c_uint32), ("n_items", ctypes.c_uint32), ("items", KxFieldRange * 16), ("ofs_len", ctypes.c_uint32),
+                ("ofs", ctypes.c_uint8 * 8), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 4)]
+
+
+KX_PROJECT_WORDS, KX_PROJECT_UNQUOTE = 1, 2
+
+
+def _field_item_array(items):
+    """Items as written → (KxFieldRange * 16, n_items)."""
+    a = (KxFieldRange * 16)()
+    for j, (lo, hi) in enumerate(items):
+        a[j].lo, a[j].hi = lo, hi or 0
+    return a, len(items)
+
+
+def _check_ofs(ofs):
+    """An output field separator: 0 to 8 bytes → bytes."""
+    if not isinstance(ofs, (bytes, bytearray)):
+        raise TypeError("ofs: bytes of length 0 to 8, not %s" % type(ofs).__name__)
+    if len(ofs) > 8:
+        raise ValueError("ofs: 0 to 8 bytes, not %d" % len(ofs))
+    return bytes(ofs)
+
+
+def _check_ofs_codec(what, ofs, q, e, special):
+    """On values OFS is what the spelling protects: one byte that is not the quote, the escape or a special byte."""
+    if len(ofs) != 1:
+        raise ValueError("%s: with unquote= the ofs is exactly one byte, not %d" % (what, len(ofs)))
+    if ofs[0] in (q, e) or ofs[0] in special:
+        raise ValueError("%s: with unquote= the ofs cannot be the quote, the escape or a special byte" % what)
+
+
 class KxFieldCodec(ctypes.Structure):
     """include/kxhip.h::kx_field_codec."""
     _fields_ = [("size", ctypes.c_uint32), ("n_special", ctypes.c_uint32), ("special", ctypes.c_uint8 * 8), ("reserved", ctypes.c_uint32 * 4)]
@@ -1044,6 +1132,12 @@ def load_engine():
         lib.kx_run_batch_field_words.argtypes = lib.kx_run_batch_field_values.argtypes
         lib.kx_run_records_fd_field_words.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.POINTER(KxFieldRange),
                                                       u32, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
+        lib.kx_run_batch_field_project.argtypes = [vp, vp, vp, u64, ctypes.POINTER(KxBatchFieldList), ctypes.POINTER(KxFieldCodec),
+                                                   ctypes.POINTER(KxFieldProject), vp, sz, vp, vp, vp, ctypes.POINTER(sz),
+                                                   ctypes.POINTER(KxBatchStats), vp]
+        lib.kx_run_records_fd_field_project.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.POINTER(KxFieldRange),
+                                                        u32, ctypes.c_uint8, ctypes.c_char_p, u32, u32, ctypes.c_int,
+                                                        ctypes.POINTER(KxRecordsStats)]
         lib.kx_run_records_fd_fields.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), u32, ctypes.c_uint8,
                                                  ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
         lib.kx_run_records_fd_opts.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.c_int,
@@ -1515,11 +1609,12 @@ class Program:
             frame.suffix[:len(suffix)] = bytes(suffix)
         return self._run_batch_call("run_batch_tensor", values, offsets, out, frame, None)
 
-    def _run_batch_call(self, what, values, offsets, out, frame, fields, codec=None, words=False):
+    def _run_batch_call(self, what, values, offsets, out, frame, fields, codec=None, words=False, proj=None):
         """The device part of run_batch_tensor (`frame`: a KxBatchFrame or None), run_batch_fields_tensor (`fields`: a
         KxBatchFields), run_batch_field_list_tensor (`fields`: a KxBatchFieldList, which adds the fail_field tensor to the
         result), run_batch_field_values_tensor (the same with `codec`: a KxFieldCodec) and run_batch_field_words_tensor (`words`;
-        `codec` a KxFieldCodec or None): the checks that need the tensors' device, the buffers, the size query and the call."""
+        `codec` a KxFieldCodec or None) and run_batch_field_project_tensor (`proj`: a KxFieldProject, whose flags say whether the
+        fields are words): the checks that need the tensors' device, the buffers, the size query and the call."""
         import torch
         if not values.is_cuda:
             raise EngineError("%s: values must be on a HIP device (there is no CPU fallback)" % what)
@@ -1544,7 +1639,13 @@ class Program:
             st = KxBatchStats()
             bptr = ctypes.c_void_p(buf.data_ptr() if buf is not None and buf.numel() else None)
             bcap = buf.numel() if buf is not None else 0
-            if words:
+            if proj is not None:
+                rc = self._lib.kx_run_batch_field_project(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
+                                                          ctypes.byref(fields), ctypes.byref(codec) if codec is not None else None,
+                                                          ctypes.byref(proj), bptr, bcap, ctypes.c_void_p(out_off.data_ptr()),
+                                                          ctypes.c_void_p(docs.data_ptr()), ctypes.c_void_p(ffield.data_ptr()),
+                                                          ctypes.byref(ol), ctypes.byref(st), ctypes.c_void_p(stream))
+            elif words:
                 rc = self._lib.kx_run_batch_field_words(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
                                                         ctypes.byref(fields), ctypes.byref(codec) if codec is not None else None, bptr,
                                                         bcap, ctypes.c_void_p(out_off.data_ptr()), ctypes.c_void_p(docs.data_ptr()),
@@ -1718,6 +1819,52 @@ class Program:
         spec.suffix[:len(suffix)] = bytes(suffix)
         return self._run_batch_call(what, values, offsets, out, None, spec, codec, words=True)
 
+    def run_batch_field_project_tensor(self, values, offsets, items, ofs, fs=b"\t", blanks=False, quote=None, escape=None, unquote=False,
+                                       special=b"\n", sep_len=0, last_whole=False, keep_sep=True, suffix=b"", out=None):
+        """Field mode, projected (kx_run_batch_field_project, project_records_model): the program runs once on every field of the
+        union of `items` (a parse_field_order result, or 1 to 16 ints and (lo, hi) pairs in any order), as
+        run_batch_field_list_tensor runs it — with `blanks` on the words, as run_batch_field_words_tensor (`fs` is then not used);
+        with `unquote` on the values, as run_batch_field_values_tensor — and an accepted record writes only the outputs (with
+        `unquote` their spellings, which protect the one byte of `ofs` in place of `fs`), item by item in the written order, joined
+        by the 0 to 8 bytes `ofs`, then separator and suffix as there.  Returns the six tensors of run_batch_field_list_tensor;
+        fail_field is the lowest rejected field number whatever the order."""
+        what = "run_batch_field_project_tensor"
+        _check_batch_args(values, offsets)
+        (items, ranges), sep_len, ofs = _check_field_items(items), _check_sep_len(sep_len), _check_ofs(ofs)
+        for name, v in (("blanks", blanks), ("unquote", unquote), ("last_whole", last_whole), ("keep_sep", keep_sep)):
+            if not isinstance(v, bool):
+                raise TypeError("%s: %s must be True or False, not %s" % (what, name, type(v).__name__))
+        f = 0 if blanks else _check_fs(fs, quote, escape)
+        codec = None
+        if unquote:
+            q, e, special = _check_codec(what, quote, escape, special)
+            if blanks and len(special) > 7:
+                raise ValueError("%s: special must be 0 to 7 bytes (the tab is added), not %d" % (what, len(special)))
+            _check_ofs_codec(what, ofs, q, e, special + (b"\t" if blanks else b""))
+            codec = KxFieldCodec(size=ctypes.sizeof(KxFieldCodec), n_special=len(special))
+            codec.special[:len(special)] = special
+        else:
+            q = None if quote is None else _one_byte(quote, "quote character")
+            e = None if escape is None else _one_byte(escape, "escape character")
+            if q is not None and q == e:
+                raise ValueError("escape character: %r is also the quote character" % bytes([e]))
+        if blanks:
+            _check_not_blank(quote, escape, special=special if unquote else b"")
+        if not isinstance(suffix, (bytes, bytearray)):
+            raise TypeError("%s: suffix must be bytes of length 0 to 8, not %s" % (what, type(suffix).__name__))
+        if len(suffix) > 8:
+            raise ValueError("%s: suffix must be 0 to 8 bytes, not %d" % (what, len(suffix)))
+        arr, nr = _field_range_array(ranges)
+        spec = KxBatchFieldList(size=ctypes.sizeof(KxBatchFieldList), n_ranges=nr, ranges=arr, fs=f, quote=-1 if q is None else q,
+                                escape=-1 if e is None else e, sep_len=sep_len, last_whole=1 if last_whole else 0,
+                                keep_sep=1 if keep_sep else 0, suffix_len=len(suffix))
+        spec.suffix[:len(suffix)] = bytes(suffix)
+        iarr, ni = _field_item_array(items)
+        proj = KxFieldProject(size=ctypes.sizeof(KxFieldProject), n_items=ni, items=iarr, ofs_len=len(ofs),
+                              flags=KX_PROJECT_WORDS if blanks else 0)
+        proj.ofs[:len(ofs)] = ofs
+        return self._run_batch_call(what, values, offsets, out, None, spec, codec, proj=proj)
+
     def fields_kernel_stats(self):
         """kx_fields_stats: HIP-event times of field mode's own kernels, summed over this program's calls (collect_timing)."""
         st = KxFieldsKernelStats()
@@ -1796,6 +1943,26 @@ class Program:
         return field, fields, None
 
     @staticmethod
+    def _check_only(what, only, ofs, field, fields, fs, blanks):
+        """The `only=` and `ofs=` keywords of record mode: `only` with `field` or `fields`, `ofs` with `only` → (items, ofs): the
+        list as written (a `field=K` is the list K-K) and the output field separator, whose default is `fs` — a tab if that is
+        not given — or one space with `blanks`; (None, None) without `only`."""
+        if not isinstance(only, bool):
+            raise TypeError("%s: only must be True or False, not %s" % (what, type(only).__name__))
+        if not only:
+            if ofs is not None:
+                raise ValueError("%s: ofs= needs only=" % what)
+            return None, None
+        if field is None and fields is None:
+            raise ValueError("%s: only= needs field= or fields=" % what)
+        if field is not None and fields is not None:
+            raise ValueError("%s: field= and fields= exclude each other" % what)
+        items, _ = _check_field_items([_check_field(field)] if fields is None else fields)
+        if ofs is None:
+            ofs = b" " if blanks else b"\t" if fs is None else bytes([_one_byte(fs, "field separator")])
+        return items, _check_ofs(ofs)
+
+    @staticmethod
     def _check_rs_alone(rs, sep, quote, escape, what):
         """The `rs=` keyword of record mode: 1 to 8 bytes, with the default `sep` and neither `quote` nor `escape`."""
         rs = _check_rs(rs)
@@ -1806,7 +1973,7 @@ class Program:
         return rs
 
     def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None, batch_actions=True, rs=None, chomp=False, ors=b"",
-                    field=None, fs=None, fields=None, unquote=False, blanks=False):
+                    field=None, fs=None, fields=None, unquote=False, blanks=False, only=False, ofs=None):
         """Record mode on bytes: every record of `data` (split after each `sep` byte, kx_split_records on the device) is a
         whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage).  With a `quote` byte
         a separator inside quotes ends no record (kx_split_records_quoted from parity 0).  With an `escape` byte an escaped
@@ -1826,10 +1993,16 @@ class Program:
         unquote_field_model, requote_field_model); `field=K` is then the list K-K, and `pos` counts inside the value.  With
         `blanks` (with `field` or `fields`, not with `fs`, whose default is a tab) the fields are the words between the record's
         live spaces and tabs and every blank is copied as it is (kx_run_batch_field_words, blank_field_list_records_model);
-        `field=K` is then the list K-K, and a record without any word gives NoFieldError(0)."""
+        `field=K` is then the list K-K, and a record without any word gives NoFieldError(0).  With `only` (with `field` or `fields`)
+        an accepted record gives the outputs of its selected fields alone, in the order the `fields` sequence has them — items
+        may overlap and repeat — joined by the 0 to 8 bytes `ofs` (default `fs`, or one space with `blanks`), then separator and
+        `ors` as ever (kx_run_batch_field_project, project_records_model); with `unquote` the spellings protect `ofs`, one byte."""
         if not isinstance(data, (bytes, bytearray, memoryview)):
             raise TypeError("run_records: data must be bytes, not %s" % type(data).__name__)
         chomp, ors = _check_chomp(chomp), _check_ors(ors)
+        items, ofs = self._check_only("run_records", only, ofs, field, fields, fs, blanks)
+        if items is not None:
+            field, fields = None, list(items)
         field, fields = self._check_unquote("run_records", unquote, field, fields, quote, escape)
         field, fields, fs = self._check_blanks("run_records", blanks, field, fields, fs, sep, quote, escape, rs)
         if field is not None and fields is not None:
@@ -1873,7 +2046,11 @@ class Program:
         trim = (len(rs) if rs is not None else 1) if chomp else 0
         ffield = None
         with self._batch_actions_for_call(batch_actions):
-            if blanks:
+            if items is not None:
+                out, ooff, status, fpos, fstage, ffield = self.run_batch_field_project_tensor(
+                    v, offs, items, ofs, fs, blanks, quote, escape, unquote=unquote, special=sep_byte,
+                    sep_len=len(rs) if rs is not None else 1, last_whole=bool(tail and data), keep_sep=not chomp, suffix=ors)
+            elif blanks:
                 out, ooff, status, fpos, fstage, ffield = self.run_batch_field_words_tensor(
                     v, offs, fields, quote, escape, unquote=unquote, special=sep_byte, sep_len=len(rs) if rs is not None else 1,
                     last_whole=bool(tail and data), keep_sep=not chomp, suffix=ors)
@@ -1899,7 +2076,7 @@ class Program:
                 for i in range(len(status))]
 
     def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None, batch_actions=True, rs=None, chomp=False,
-                       ors=b"", field=None, fs=None, fields=None, unquote=False, blanks=False):
+                       ors=b"", field=None, fs=None, fields=None, unquote=False, blanks=False, only=False, ofs=None):
         """kx_run_records_fd: the stream on in_fd in record mode, outputs to out_fd, one line per rejected record to report_fd
         (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected.  With a `quote`
         byte, kx_run_records_fd_quoted: a separator inside quotes ends no record.  With an `escape` byte,
@@ -1911,7 +2088,11 @@ class Program:
         With `fields` (as in run_records; not with `field`), kx_run_records_fd_field_list: the program runs on every field of the
         list, and a record with a rejected field is reported once, with the field's number.  With `unquote` (as in run_records),
         kx_run_records_fd_field_values: the program runs on the values of the selected fields, which are spelled again behind it.
-        With `blanks` (as in run_records), kx_run_records_fd_field_words: the fields are the words between live spaces and tabs."""
+        With `blanks` (as in run_records), kx_run_records_fd_field_words: the fields are the words between live spaces and tabs.
+        With `only` and `ofs` (as in run_records), kx_run_records_fd_field_project: only the selected fields' outputs are written."""
+        items, ofs = self._check_only("run_records_fd", only, ofs, field, fields, fs, blanks)
+        if items is not None:
+            field, fields = None, list(items)
         field, fields = self._check_unquote("run_records_fd", unquote, field, fields, quote, escape)
         field, fields, fs = self._check_blanks("run_records_fd", blanks, field, fields, fs, sep, quote, escape, rs)
         for name, fd in (("in_fd", in_fd), ("out_fd", out_fd), ("report_fd", report_fd)):
@@ -1948,6 +2129,12 @@ class Program:
                     name, args = "kx_run_records_fd_field_values" if unquote else "kx_run_records_fd_field_list", (ctypes.byref(o), arr, nr, f)
                     if blanks:
                         name, args = "kx_run_records_fd_field_words", (ctypes.byref(o), arr, nr, 1 if unquote else 0)
+                    if items is not None:
+                        if unquote:
+                            _check_ofs_codec("run_records_fd", ofs, q, e, bytes([s]) + (b"\t" if blanks else b""))
+                        iarr, ni = _field_item_array(items)
+                        name, args = "kx_run_records_fd_field_project", (ctypes.byref(o), iarr, ni, f, ofs, len(ofs),
+                                                                         (KX_PROJECT_WORDS if blanks else 0) | (KX_PROJECT_UNQUOTE if unquote else 0))
             else:                                        # the mode's own entry point
                 name, args = (("kx_run_records_fd", (s,)), ("kx_run_records_fd_quoted", (s, q)), ("kx_run_records_fd_escaped", (s, qi, e)),
                               ("kx_run_records_fd_rs", (rs, len(rs or b""))))[mode]
