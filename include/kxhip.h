@@ -209,7 +209,15 @@ int kx_stage_describe_cfg(const void* blob, size_t blob_len, uint32_t stage, con
 
 /* Whole program (all pipeline stages) over one device-resident input.
  * d_out may be NULL with cap 0 to query the exact output size (returned in
- * *out_len with KX_E_CAPACITY).  Blocks until the result is complete. */
+ * *out_len with KX_E_CAPACITY).  Blocks until the result is complete.
+ * What the call writes and reads (tests/test_run_device_gpu.py holds it to this):
+ *   - d_out is 16-byte aligned, KX_E_ARG otherwise, before anything is launched.  (A program whose last stage has register actions
+ *     copies its result bytewise and takes any address.)
+ *   - Nothing outside d_out[0, *out_len) is written, whatever `cap` says: room beyond the result is not scratch space.
+ *   - On KX_MATCH_ERROR, KX_E_CAPACITY and KX_E_ARG d_out is untouched.
+ *   - d_in may have any alignment (an address that is not 16-byte aligned costs a copy of the input), is never written, and no byte
+ *     outside d_in[0, n) influences the result.
+ *   - All device work is queued on `stream` (NULL: the default stream), behind whatever the caller has queued there. */
 int kx_run_device(kx_program* prog, const void* d_in, size_t n, void* d_out, size_t cap, size_t* out_len,
                   kx_stats* stats, void* stream);
 
@@ -615,6 +623,9 @@ int kx_shard_forward(kx_shard* s, kx_fwd_summary* out);
 int kx_shard_fix_head(kx_shard* s, uint32_t incoming_state, kx_fwd_summary* out);
 int kx_shard_backward(kx_shard* s, kx_bwd_summary* out);
 int kx_shard_resolve(kx_shard* s, uint32_t end_leaf, uint64_t* out_len);
+/* Writes the shard's out_len bytes (kx_shard_resolve's) to d_out and nothing outside d_out[0, out_len), whatever `cap` says.  d_out is
+ * 16-byte aligned: KX_E_ARG otherwise; cap < out_len is KX_E_CAPACITY; d_out is untouched on both.  The shard's input (16-byte aligned,
+ * kx_shard_begin) is never written, and no byte outside its [0, n) influences the result. */
 int kx_shard_emit(kx_shard* s, void* d_out, size_t cap);
 void kx_shard_stats(kx_shard* s, kx_stats* stats);
 void kx_shard_end(kx_shard* s);

@@ -1575,7 +1575,11 @@ class Program:
         return ol.value
 
     def run_tensor(self, t, out=None):
-        """torch uint8 CUDA tensor → torch uint8 CUDA tensor (device-resident both ends)."""
+        """torch uint8 CUDA tensor → torch uint8 CUDA tensor (device-resident both ends).
+        out=: the caller's buffer (include/kxhip.h, kx_run_device).  Its address is 16-byte aligned (EngineError otherwise; a program whose
+        last stage has register actions takes any address); nothing outside out[0, result length) is written, whatever out.numel() is;
+        on a MatchError and on "output buffer too small" `out` is untouched.  `t` may have any alignment, is never written, and no byte
+        outside t[0, n) influences the result."""
         import torch
         assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
         n = t.numel()
