@@ -597,6 +597,61 @@ int kx_run_records_fd_field_project(kx_program* p, int in_fd, int out_fd, const 
                                     uint32_t n_items, uint8_t fs, const uint8_t* ofs, uint32_t ofs_len, uint32_t flags, int report_fd,
                                     kx_records_stats* stats);
 
+/* ---- header rows, and fields selected by column name (`BIN --records --header[=N] [--field=LIST with names] …`) -------------------
+ * The first `header` records of the stream are HEADER records: the program never runs on them, R of the report lines and
+ * kx_records_stats::records count them.  Without KX_TABLE_ONLY each is written as its body, its own separator unless o->chomp (a
+ * tail has none), then o->ors; nothing is looked for in it.  With KX_TABLE_ONLY it is projected as an accepted data record whose
+ * program is the identity (kx_run_batch_field_header); one with fewer than `need` cells is reported "Record R has no field K!",
+ * writes nothing and counts as rejected.
+ *   An item with lo == 0 is a NAME, names[hi][0, name_len[hi]).  Names are resolved once, when header record `header` is in hand:
+ * its body's cells are cut by the live `fs` bytes of o's mode (KX_TABLE_WORDS: into words); a cell's name is its bytes, and with a
+ * quote or an escape byte its value (host.unquote_field_model), with or without KX_TABLE_UNQUOTE; if that record is the stream's
+ * first and begins with EF BB BF, the names are cut behind those bytes.  A name selects the lowest-numbered cell that has it.  From
+ * then on the run is that of the same items as numbers; a list with a name always reports "… in field K of record R!".  With
+ * KX_TABLE_ONLY and names, the header records in front of record `header` are held until it has come: a stream that ends before
+ * it writes none of them.  A name no cell has, or a resolved union of more than 8 ranges: KX_E_HEADER, no byte of record `header`
+ * or of anything behind it is written, and kx_last_error names the entry point and the name.  A stream that ends before record
+ * `header` resolves nothing and returns 0.
+ *   With header == 0 (names are then refused) the call is exactly the entry point its flags name: no items kx_run_records_fd_opts;
+ * KX_TABLE_SINGLE kx_run_records_fd_fields; KX_TABLE_ONLY kx_run_records_fd_field_project with the items as written; else
+ * KX_TABLE_WORDS kx_run_records_fd_field_words, KX_TABLE_UNQUOTE kx_run_records_fd_field_values, no flag
+ * kx_run_records_fd_field_list, each with the normal form of the items' union.
+ * KX_E_ARG before any device work: those entry points' own refusals; a wrong `size`; non-zero pad or reserved words; unknown flag
+ * bits; flags without items; more than 16 items or names; an item with lo >= 1 and 0 < hi < lo; a name index >= n_names; a name of
+ * 0 or more than 255 bytes; a null name pointer; names with header == 0; KX_TABLE_SINGLE with another flag or with anything but
+ * one closed number item; without names, a union of more than 8 ranges. */
+#define KX_E_HEADER (-6)        /* a name of the field list is no cell of the header record, or the resolved list has too many ranges */
+#define KX_TABLE_WORDS 1u       /* the fields are the words between blanks (`fs` is not used) */
+#define KX_TABLE_UNQUOTE 2u     /* the program runs on the fields' values */
+#define KX_TABLE_ONLY 4u        /* only the selected fields are written, in the items' order, joined by ofs */
+#define KX_TABLE_SINGLE 8u      /* one item K-K that reports as kx_run_records_fd_fields ("… in record R!") */
+typedef struct kx_records_table {
+  uint32_t size;              /* sizeof(kx_records_table) */
+  uint32_t header;            /* N: the first N records are header records (0: none) */
+  uint32_t flags;             /* KX_TABLE_* */
+  uint32_t n_items;           /* 0: no field mode */
+  kx_field_range items[16];   /* as written.  lo >= 1: numbers, as in kx_field_project; lo == 0: the name names[hi] */
+  uint32_t n_names;
+  const uint8_t* names[16];
+  uint32_t name_len[16];      /* 1 to 255 */
+  uint8_t fs;                 /* the field separator (not with KX_TABLE_WORDS) */
+  uint8_t pad[3];             /* must be 0 */
+  uint32_t ofs_len;           /* KX_TABLE_ONLY: 0 to 8 */
+  uint8_t ofs[8];
+  uint32_t reserved[4];       /* must be 0 */
+} kx_records_table;
+int kx_run_records_fd_table(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_records_table* t, int report_fd,
+                            kx_records_stats* stats);
+
+/* kx_run_batch_field_project in every word of its contract, with the identity in the program's place for every record of the call:
+ * the selected fields themselves (with a codec: the spellings of their values) are what is projected, no record is ever rejected
+ * by the program (status 2, too few fields, remains), and no document is routed or replayed.  It is the route a header record takes
+ * under KX_TABLE_ONLY. */
+int kx_run_batch_field_header(kx_program* prog, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* list,
+                              const kx_field_codec* codec /* or NULL */, const kx_field_project* proj, void* d_out, size_t cap,
+                              uint64_t* d_out_off, kx_batch_doc* d_docs, uint32_t* d_fail_field, size_t* out_len, kx_batch_stats* stats,
+                              void* stream);
+
 /* ---- sharded execution: one contiguous shard of the input per GPU -------------
  * Per stage and per rank:
  *   kx_shard_begin → kx_shard_forward → [exchange kx_fwd_summary] → kx_shard_fix_head

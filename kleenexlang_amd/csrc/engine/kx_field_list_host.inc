@@ -37,11 +37,14 @@ int checkFieldList(const kx_batch_field_list& l, const char* who) {
 // is not used, and the value kernels' field separator is the space.  Nothing else differs.  With `proj`
 // (kx_run_batch_field_project, kx_field_project_host.inc, whose checks have passed) steps 1 to 4v are the same but for the value
 // kernels' field separator, which is the OFS byte, and steps 5 and 6 are k_fpsplen and k_fpsplice (kx_field_project.inc) over the
-// items' table; without it every launch and every argument is what it is without the parameter.
+// items' table; without it every launch and every argument is what it is without the parameter.  With `identity`
+// (kx_run_batch_field_header; with `proj` only) step 4 is left out: the gathered fields — with a codec the decoded values — and
+// their offsets stand in for the program's outputs and theirs, and the document records are zeroed (every one accepted); steps 4v,
+// 5 and 6 run as they are.  Without it every launch and every argument is what it is without the parameter.
 int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* l,
                  const kx_field_codec* codec, void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs, uint32_t* d_fail_field,
                  size_t* out_len, kx_batch_stats* stats, void* stream, const char* who, bool words = false,
-                 const kx_field_project* proj = nullptr) {
+                 const kx_field_project* proj = nullptr, bool identity = false) {
   if (n_docs && (!d_in_off || !d_out_off || !d_docs)) return setErr(KX_E_ARG, std::string(who) + ": offsets, output offsets and document records are required");
   if (n_docs >= 0xFFFFFFFFull) return setErr(KX_E_ARG, std::string(who) + ": at most 2^32 - 2 documents per call");
   *out_len = 0;
@@ -157,6 +160,7 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
   unsigned long long *fb = nullptr, *fe = nullptr, *coff = nullptr, *poff = nullptr;
   kx_batch_doc* drec = nullptr;
   const uint8_t* spliced = nullptr;   // with a codec: the spellings, which k_flsplice takes for the program's outputs
+  const uint8_t* pbytes = nullptr;    // the program's outputs (with `identity`: the documents themselves)
   if (ndocs) {
     // 2. the documents' bounds, and the scan of their lengths
     for (BatchWs::Buf* b : {&W.fb, &W.fe}) if (!rc) rc = BatchWs::ensure(*b, ndocs * 8);
@@ -222,22 +226,29 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
       docs_in = V->ucomp.p; docs_off = uoff;
     }
     // 4. the program on every selected field
-    size_t pl = 0;
-    const size_t slack = V ? 16 : 0;              // (k_fvenclen and k_fvencode read the outputs' last granule whole)
-    rc = BatchWs::ensure(W.pout, docs_total + docs_total / 2 + 4096 + slack);
-    if (rc) return rc;
-    rc = kx_run_batch(p, docs_in, (const uint64_t*)docs_off, ndocs, W.pout.p, W.pout.cap - slack, (uint64_t*)poff, drec, &pl, &bst, stream);
-    if (rc == KX_E_CAPACITY) {
-      rc = BatchWs::ensure(W.pout, pl + 16 + slack);
+    if (identity) {                               // (both compact buffers end in 32 bytes of slack)
+      HIPCHECK(hipMemsetAsync(drec, 0, ndocs * sizeof(kx_batch_doc), sm));
+      pbytes = (const uint8_t*)docs_in;
+      poff = const_cast<unsigned long long*>(docs_off);
+    } else {
+      size_t pl = 0;
+      const size_t slack = V ? 16 : 0;              // (k_fvenclen and k_fvencode read the outputs' last granule whole)
+      rc = BatchWs::ensure(W.pout, docs_total + docs_total / 2 + 4096 + slack);
       if (rc) return rc;
       rc = kx_run_batch(p, docs_in, (const uint64_t*)docs_off, ndocs, W.pout.p, W.pout.cap - slack, (uint64_t*)poff, drec, &pl, &bst, stream);
+      if (rc == KX_E_CAPACITY) {
+        rc = BatchWs::ensure(W.pout, pl + 16 + slack);
+        if (rc) return rc;
+        rc = kx_run_batch(p, docs_in, (const uint64_t*)docs_off, ndocs, W.pout.p, W.pout.cap - slack, (uint64_t*)poff, drec, &pl, &bst, stream);
+      }
+      if (rc != 0 && rc != KX_MATCH_ERROR) return rc;
+      pbytes = (const uint8_t*)W.pout.p;
     }
-    if (rc != 0 && rc != KX_MATCH_ERROR) return rc;
     // 4v. the spellings of the outputs take the outputs' place
     if (V) {
       unsigned long long* qoff = (unsigned long long*)V->qoff.p;
       if (timing) HIPCHECK(hipEventRecord(V->ev[2], sm));
-      hipLaunchKernelGGL(k_fvenclen, dim3(dgrid), dim3(FLD_BT), 0, sm, (const uint8_t*)W.pout.p, (const unsigned long long*)poff, (const kx_batch_doc*)drec,
+      hipLaunchKernelGGL(k_fvenclen, dim3(dgrid), dim3(FLD_BT), 0, sm, pbytes, (const unsigned long long*)poff, (const kx_batch_doc*)drec,
                          ndocs, C, (uint8_t*)V->vflag.p, len);
       scanLens(len, ndocs, qoff);
       HIPCHECK(hipGetLastError());
@@ -246,7 +257,7 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
       HIPCHECK(hipStreamSynchronize(sm));
       rc = BatchWs::ensure(V->qout, qtotal + 16);
       if (rc) return rc;
-      hipLaunchKernelGGL(k_fvencode, dim3(dgrid), dim3(FLD_BT), 0, sm, (const uint8_t*)W.pout.p, (const unsigned long long*)poff, (const kx_batch_doc*)drec,
+      hipLaunchKernelGGL(k_fvencode, dim3(dgrid), dim3(FLD_BT), 0, sm, pbytes, (const unsigned long long*)poff, (const kx_batch_doc*)drec,
                          ndocs, C, (const uint8_t*)V->vflag.p, (const unsigned long long*)qoff, (uint8_t*)V->qout.p);
       if (timing) HIPCHECK(hipEventRecord(V->ev[3], sm));
       HIPCHECK(hipGetLastError());
@@ -281,12 +292,12 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
   if (timing) HIPCHECK(hipEventRecord(W.ev[10], sm));
   if (total && proj)
     hipLaunchKernelGGL(k_fpsplice, granGrid(total), dim3(FLD_GT), 0, sm, in, off, (unsigned long long)nd, P, (const unsigned long long*)d0,
-                       spliced ? spliced : (const uint8_t*)W.pout.p, (const unsigned long long*)poff, (const unsigned long long*)d_out_off, total,
+                       spliced ? spliced : pbytes, (const unsigned long long*)poff, (const unsigned long long*)d_out_off, total,
                        (uint8_t*)d_out);
   else if (total)
     hipLaunchKernelGGL(k_flsplice, granGrid(total), dim3(FLD_GT), 0, sm, in, off, (unsigned long long)nd, L.F, (const unsigned long long*)d0,
                        (const unsigned long long*)fb, (const unsigned long long*)fe, (const unsigned long long*)coff,
-                       spliced ? spliced : (const uint8_t*)W.pout.p, (const unsigned long long*)poff, (const unsigned long long*)d_out_off, total, sfx8, (uint8_t*)d_out);
+                       spliced ? spliced : pbytes, (const unsigned long long*)poff, (const unsigned long long*)d_out_off, total, sfx8, (uint8_t*)d_out);
   if (timing) HIPCHECK(hipEventRecord(W.ev[11], sm));
   HIPCHECK(hipGetLastError());
   HIPCHECK(hipStreamSynchronize(sm));

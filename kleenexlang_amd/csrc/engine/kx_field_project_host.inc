@@ -1,7 +1,7 @@
 // kx_field_project_host.inc — the projection of field mode (kx_run_batch_field_project, include/kxhip.h; kernels in
 // kx_field_project.inc).  Included at the end of kx_engine.hip between kx_field_words_host.inc, whose rules and the two files'
 // before it it applies, and kx_records_host.inc.  The driver is kx_field_list_host.inc's runFieldList with `proj` set.  Here: the
-// rules of a kx_field_project, and the entry point.
+// rules of a kx_field_project, and the entry point; kx_run_batch_field_header is the same call with the driver's identity switch.
 
 namespace {
 
@@ -32,12 +32,10 @@ int checkFieldProjectWith(const kx_field_project& pr, const kx_batch_field_list&
   return 0;
 }
 
-}  // namespace
-
-extern "C" int kx_run_batch_field_project(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* l,
-                                          const kx_field_codec* codec, const kx_field_project* proj, void* d_out, size_t cap, uint64_t* d_out_off,
-                                          kx_batch_doc* d_docs, uint32_t* d_fail_field, size_t* out_len, kx_batch_stats* stats, void* stream) {
-  static const char* const who = "kx_run_batch_field_project";
+// what kx_run_batch_field_project and kx_run_batch_field_header (`identity`) share: the rules, then the driver
+int fieldProjectEntry(const char* who, bool identity, kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs,
+                      const kx_batch_field_list* l, const kx_field_codec* codec, const kx_field_project* proj, void* d_out, size_t cap,
+                      uint64_t* d_out_off, kx_batch_doc* d_docs, uint32_t* d_fail_field, size_t* out_len, kx_batch_stats* stats, void* stream) {
   if (!p || !out_len || !l || !proj) return setErr(KX_E_ARG, "null argument");
   if (const int rc = checkFieldProject(*proj, who)) return rc;
   const bool words = (proj->flags & KX_PROJECT_WORDS) != 0;
@@ -54,5 +52,21 @@ extern "C" int kx_run_batch_field_project(kx_program* p, const void* d_in, const
   }
   if (const int rc = checkFieldProjectWith(*proj, ll, codec ? &cc : nullptr, who)) return rc;
   return runFieldList(p, d_in, d_in_off, n_docs, &ll, codec ? &cc : nullptr, d_out, cap, d_out_off, d_docs, d_fail_field, out_len, stats, stream, who,
-                      words, proj);
+                      words, proj, identity);
+}
+
+}  // namespace
+
+extern "C" int kx_run_batch_field_project(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* l,
+                                          const kx_field_codec* codec, const kx_field_project* proj, void* d_out, size_t cap, uint64_t* d_out_off,
+                                          kx_batch_doc* d_docs, uint32_t* d_fail_field, size_t* out_len, kx_batch_stats* stats, void* stream) {
+  return fieldProjectEntry("kx_run_batch_field_project", false, p, d_in, d_in_off, n_docs, l, codec, proj, d_out, cap, d_out_off, d_docs, d_fail_field,
+                           out_len, stats, stream);
+}
+
+extern "C" int kx_run_batch_field_header(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* l,
+                                         const kx_field_codec* codec, const kx_field_project* proj, void* d_out, size_t cap, uint64_t* d_out_off,
+                                         kx_batch_doc* d_docs, uint32_t* d_fail_field, size_t* out_len, kx_batch_stats* stats, void* stream) {
+  return fieldProjectEntry("kx_run_batch_field_header", true, p, d_in, d_in_off, n_docs, l, codec, proj, d_out, cap, d_out_off, d_docs, d_fail_field,
+                           out_len, stats, stream);
 }

@@ -30,6 +30,15 @@
 // `unquote`, that codec; checkRecordsOpts has the blank rules.  Projected (kx_run_records_fd_field_project) RecordsRun holds the
 // kx_field_project beside the ranges, which are the normal form of its items' union, and calls kx_run_batch_field_project for the
 // carried record and the window's records alike, with the codec and the words flag as above.
+//
+// Header records (kx_run_records_fd_table): RecordsRun::batch splits a call whose records reach below `header` into a header part
+// and a data part; the tail flag goes to the part that holds the last record, and the carried record takes the same path, so a
+// header record may straddle windows.  A header record that is only copied is placed with device-to-device copies; projected, it
+// runs through kx_run_batch_field_header.  Record `header`'s bytes come to the host once, where kx_field_names.h cuts its cells and
+// resolves the names of the items; the run's ranges and projection are filled in from that, and the records behind it launch what
+// the numeric call launches.  No kernel is the header's own.
+
+#include "kx_field_names.h"
 
 namespace {
 
@@ -247,6 +256,14 @@ struct RecordsRun {
   kx_field_codec codec{};                              // ... on their values (size != 0: kx_run_batch_field_values; special = the separator)
   bool words = false;                                  // ... which are the body's words (kx_run_batch_field_words; fsep is not used)
   kx_field_project proj{};                             // ... projected (size != 0: kx_run_batch_field_project; ranges = the items' union)
+  uint64_t header = 0;                                 // the first `header` records are header records (kx_run_records_fd_table)
+  kx_field_range titems[KX_FIELD_ITEMS] = {};          // ... and these items, some of them names (lo = 0, hi = the index into `names`),
+  uint32_t n_titems = 0;                               //   become ranges (and proj.items) when record `header` is in hand
+  std::vector<std::string> names;
+  bool resolved = true;                                // (false: titems wait for that record)
+  const char* who = "";                                // the entry point, for a resolution that fails
+  BatchWs::Buf hstash, hoff;                           // projected by names: the header records held until the names are resolved
+  std::vector<uint64_t> hends;                         //   ... and where each ends in hstash
   SplitCarry next;                                     // what the next window's split starts from
   int report_fd = -1;
   RecWs ws;
@@ -260,7 +277,7 @@ struct RecordsRun {
   bool timing = false;
 
   ~RecordsRun() {
-    for (BatchWs::Buf* b : {&off, &ooff, &docs, &carry, &one, &longest, &ffield}) if (b->p) (void)hipFree(b->p);
+    for (BatchWs::Buf* b : {&off, &ooff, &docs, &carry, &one, &longest, &ffield, &hstash, &hoff}) if (b->p) (void)hipFree(b->p);
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
   }
 
@@ -282,10 +299,101 @@ struct RecordsRun {
     return 0;
   }
 
+  // room for `need` more bytes in *out at byte pos: a buffer too small is replaced by a larger one, its first pos bytes kept
+  int reserve(DevBuf* out, size_t pos, size_t need) {
+    if (out->cap - pos >= need) return 0;
+    DevBuf nb;
+    const int rc = fs->pool.get(pos + need + need / 8 + 4096, &nb);
+    if (rc) return rc;
+    if (pos) HIPCHECK(hipMemcpy(nb.d, out->d, pos, hipMemcpyDeviceToDevice));
+    fs->pool.put(*out);
+    *out = nb;
+    return 0;
+  }
+
+  // the names of titems against header record `header`, whose bytes are in[b, e) (its separator included unless it is the tail):
+  // ranges, and with a projection its items, are filled in from the resolver (kx_field_names.h)
+  int resolve(const uint8_t* in, uint64_t b, uint64_t e, bool tail) {
+    const uint64_t sep_len = tail ? 0 : o.mode == KX_RECORDS_RS ? o.rs_len : 1u;
+    std::vector<uint8_t> body(e - b - sep_len);
+    if (!body.empty()) HIPCHECK(hipMemcpy(body.data(), in + b, body.size(), hipMemcpyDeviceToHost));
+    const bool q = o.mode == KX_RECORDS_QUOTED || o.mode == KX_RECORDS_ESCAPED;
+    std::vector<std::string> cells;
+    kxHeaderCellNames(body.data(), body.size(), fsep, q ? o.quote : -1, o.mode == KX_RECORDS_ESCAPED ? o.escape : -1, words, header == 1, &cells);
+    kx_field_range items[KX_FIELD_ITEMS] = {};
+    uint32_t missing = 0;
+    const int bad = kxResolveFieldNames(titems, n_titems, names, cells, items, ranges, &n_ranges, &missing);
+    if (bad == 1)
+      return setErr(KX_E_HEADER, std::string(who) + ": no cell of header record " + std::to_string(header) + " is named \"" +
+                                     kxPrintableName(names[missing]) + "\"");
+    if (bad) return setErr(KX_E_HEADER, std::string(who) + ": the fields that the names of header record " + std::to_string(header) +
+                                            " select have more than 8 ranges in their normal form");
+    if (proj.size) memcpy(proj.items, items, sizeof proj.items);
+    resolved = true;
+    return 0;
+  }
+
+  // the h header records in[d_o[0], d_o[h]) (numbered from first_rec; tail: the last one is the stream's tail).  Not projected,
+  // each is placed with device-to-device copies: its body, its separator unless `chomp`, the `ors` bytes.  Projected, they run
+  // through kx_run_batch_field_header — once the names are resolved, until when they are held in hstash.  Record `header` resolves.
+  int headerPart(const uint8_t* in, const uint64_t* d_o, uint64_t h, DevBuf* out, size_t* pos, uint64_t first_rec, bool tail) {
+    std::vector<uint64_t> ho(h + 1);
+    HIPCHECK(hipMemcpy(ho.data(), d_o, (h + 1) * 8, hipMemcpyDeviceToHost));
+    const bool resolves = !resolved && first_rec + h - 1 == header;
+    if (resolves) if (const int rc = resolve(in, ho[h - 1], ho[h], tail)) return rc;
+    if (proj.size && n_titems && !names.empty()) {   // projected by names: held, and run together when the names are resolved
+      const uint64_t held = hends.empty() ? 0 : hends.back(), n = ho[h] - ho[0];
+      int rc = BatchWs::grow(hstash, held, held + n, nullptr);
+      if (rc) return rc;
+      if (n) HIPCHECK(hipMemcpy((uint8_t*)hstash.p + held, in + ho[0], n, hipMemcpyDeviceToDevice));
+      for (uint64_t i = 1; i <= h; ++i) hends.push_back(held + ho[i] - ho[0]);
+      if (!resolves) { st.records += h; return 0; }
+      std::vector<uint64_t> so(1, 0);
+      so.insert(so.end(), hends.begin(), hends.end());
+      rc = BatchWs::ensure(hoff, so.size() * 8);
+      if (rc) return rc;
+      HIPCHECK(hipMemcpy(hoff.p, so.data(), so.size() * 8, hipMemcpyHostToDevice));
+      st.records -= so.size() - 1 - h;   // (runPart counts the held ones once more)
+      hends.clear();
+      return runPart((const uint8_t*)hstash.p, (const uint64_t*)hoff.p, so.size() - 1, out, pos, 1, tail, true);
+    }
+    if (proj.size) return runPart(in, d_o, h, out, pos, first_rec, tail, true);
+    const uint64_t sep_len = o.mode == KX_RECORDS_RS ? o.rs_len : 1u, seps = h - (tail ? 1 : 0);
+    const size_t need = (size_t)(ho[h] - ho[0] - (o.chomp ? seps * sep_len : 0) + h * o.ors_len);
+    if (const int rc = reserve(out, *pos, need)) return rc;
+    uint8_t* w = (uint8_t*)out->d + *pos;
+    if (!o.chomp && !o.ors_len) {
+      if (need) HIPCHECK(hipMemcpy(w, in + ho[0], need, hipMemcpyDeviceToDevice));
+    } else {
+      for (uint64_t i = 0; i < h; ++i) {
+        const uint64_t n = ho[i + 1] - ho[i] - (o.chomp && !(tail && i == h - 1) ? sep_len : 0);
+        if (n) HIPCHECK(hipMemcpy(w, in + ho[i], n, hipMemcpyDeviceToDevice));
+        if (o.ors_len) HIPCHECK(hipMemcpy(w + n, o.ors, o.ors_len, hipMemcpyHostToDevice));
+        w += n + o.ors_len;
+      }
+    }
+    st.records += h;
+    st.out_bytes += need;
+    *pos += need;
+    return 0;
+  }
+
+  // the records in[d_o[0], d_o[ndocs]) into *out at byte pos: the header records among them (headerPart), then the rest (runPart)
+  int batch(const uint8_t* in, const uint64_t* d_o, uint64_t ndocs, DevBuf* out, size_t* pos, uint64_t first_rec, bool tail) {
+    if (ndocs == 0) return 0;
+    if (first_rec <= header) {
+      const uint64_t h = std::min<uint64_t>(ndocs, header - first_rec + 1);
+      if (const int rc = headerPart(in, d_o, h, out, pos, first_rec, tail && h == ndocs)) return rc;
+      d_o += h; ndocs -= h; first_rec += h;
+    }
+    return runPart(in, d_o, ndocs, out, pos, first_rec, tail, false);
+  }
+
   // kx_run_batch of ndocs records (offsets d_o) into *out at byte pos; a buffer too small is replaced by one of the size needed,
   // its first pos bytes kept.  Reports the rejected records (numbered from first_rec) and advances *pos.  tail: the last of
-  // these records is the stream's tail (it has no separator to strip).
-  int batch(const uint8_t* in, const uint64_t* d_o, uint64_t ndocs, DevBuf* out, size_t* pos, uint64_t first_rec, bool tail) {
+  // these records is the stream's tail (it has no separator to strip).  identity: they are header records under a projection
+  // (kx_run_batch_field_header).
+  int runPart(const uint8_t* in, const uint64_t* d_o, uint64_t ndocs, DevBuf* out, size_t* pos, uint64_t first_rec, bool tail, bool identity) {
     if (ndocs == 0) return 0;
     kx_batch_frame fr{};
     fr.trim = o.chomp ? (o.mode == KX_RECORDS_RS ? o.rs_len : 1u) : 0u;
@@ -309,6 +417,9 @@ struct RecordsRun {
     ll.suffix_len = fl.suffix_len;
     memcpy(ll.suffix, fl.suffix, sizeof ll.suffix);
     auto run = [&](void* d_out, size_t cap, size_t* ol, kx_batch_stats* bs) {
+      if (identity)
+        return kx_run_batch_field_header(p, in, d_o, ndocs, &ll, codec.size ? &codec : nullptr, &proj, d_out, cap, (uint64_t*)ooff.p,
+                                         (kx_batch_doc*)docs.p, (uint32_t*)ffield.p, ol, bs, nullptr);
       if (n_ranges && proj.size)
         return kx_run_batch_field_project(p, in, d_o, ndocs, &ll, codec.size ? &codec : nullptr, &proj, d_out, cap, (uint64_t*)ooff.p,
                                           (kx_batch_doc*)docs.p, (uint32_t*)ffield.p, ol, bs, nullptr);
@@ -565,7 +676,7 @@ int checkRecordsOpts(const kx_records_opts& o, const char* who, int fs = -1, boo
 // the stream on in_fd in record mode as `o` says (checkRecordsOpts has passed)
 int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o, int report_fd, kx_records_stats* stats, uint32_t field = 0,
                  uint8_t fsep = 0, const kx_field_range* ranges = nullptr, uint32_t n_ranges = 0, bool values = false, bool words = false,
-                 const kx_field_project* proj = nullptr) {
+                 const kx_field_project* proj = nullptr, const kx_records_table* t = nullptr, const char* who = "") {
   if (!p) return setErr(KX_E_ARG, "null argument");
   if (p->cfg.phase) return setErr(KX_E_ARG, "record mode runs every phase: kx_config::phase must be 0");
   const double t_begin = FdStream::nowMs();
@@ -582,6 +693,15 @@ int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o,
   R.n_ranges = n_ranges; R.words = words;
   if (n_ranges) memcpy(R.ranges, ranges, n_ranges * sizeof(kx_field_range));
   if (proj) R.proj = *proj;
+  if (t) {   // header records, and items that may be names (checkTable has passed): without a name the caller has resolved them
+    R.header = t->header; R.who = who;
+    for (uint32_t j = 0; j < t->n_items; ++j) if (t->items[j].lo == 0) R.resolved = false;
+    if (!R.resolved) {
+      R.n_titems = t->n_items;
+      memcpy(R.titems, t->items, sizeof R.titems);
+      for (uint32_t j = 0; j < t->n_names; ++j) R.names.emplace_back((const char*)t->names[j], t->name_len[j]);
+    }
+  }
   if (values) { R.codec.size = sizeof R.codec; R.codec.n_special = 1; R.codec.special[0] = o.sep; }
   R.timing = p->cfg.collect_timing != 0;
   int rc = 0;
@@ -700,4 +820,84 @@ extern "C" int kx_run_records_fd_field_project(kx_program* p, int in_fd, int out
   memcpy(pr.items, items, n_items * sizeof(kx_field_range));
   if (ofs_len) memcpy(pr.ofs, ofs, ofs_len);
   return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, 0, words ? (uint8_t)0 : fs, ranges, n_ranges, unquote, words, &pr);
+}
+
+namespace {
+
+// the rules of a kx_records_table beside its options, found before any device work
+int checkTable(const kx_records_opts& o, const kx_records_table& t, const char* who) {
+  auto no = [&](const char* what) { return setErr(KX_E_ARG, std::string(who) + ": " + what); };
+  if (t.size != sizeof(kx_records_table)) return no("kx_records_table::size is not this library's");
+  if (t.pad[0] || t.pad[1] || t.pad[2]) return no("reserved words must be 0");
+  for (uint32_t r : t.reserved) if (r) return no("reserved words must be 0");
+  if (t.flags & ~(KX_TABLE_WORDS | KX_TABLE_UNQUOTE | KX_TABLE_ONLY | KX_TABLE_SINGLE)) return no("unknown flag bits");
+  if (t.n_items > KX_FIELD_ITEMS) return no("at most 16 items");
+  if (t.n_names > KX_FIELD_ITEMS) return no("at most 16 names");
+  if (t.ofs_len > 8) return no("the output field separator is at most 8 bytes");
+  if (!t.n_items && t.flags) return no("flags need items");
+  for (uint32_t j = 0; j < t.n_names; ++j) {
+    if (!t.names[j]) return no("a null name pointer");
+    if (t.name_len[j] < 1 || t.name_len[j] > KX_FIELD_NAME_MAX) return no("a name has 1 to 255 bytes");
+  }
+  bool named = false;
+  for (uint32_t j = 0; j < t.n_items; ++j) {
+    const kx_field_range& it = t.items[j];
+    if (it.lo == 0) {
+      named = true;
+      if (it.hi >= t.n_names) return no("a name index is not below n_names");
+    } else if (it.hi != 0 && it.hi < it.lo) {
+      return no("a number item needs hi = 0 (open) or hi >= lo");
+    }
+  }
+  if (named && !t.header) return no("names need header >= 1");
+  if ((t.flags & KX_TABLE_SINGLE) && (t.flags != KX_TABLE_SINGLE || t.n_items != 1 || t.items[0].lo == 0 || t.items[0].hi != t.items[0].lo))
+    return no("KX_TABLE_SINGLE comes alone, with one closed number item K-K");
+  const bool words = (t.flags & KX_TABLE_WORDS) != 0, unquote = (t.flags & KX_TABLE_UNQUOTE) != 0, only = (t.flags & KX_TABLE_ONLY) != 0;
+  if (const int rc = words ? checkRecordsOpts(o, who, -1, true) : checkRecordsOpts(o, who, t.n_items ? (int)t.fs : -1)) return rc;
+  if (unquote && o.mode != KX_RECORDS_QUOTED && o.mode != KX_RECORDS_ESCAPED) return no("values need a quote or an escape byte");
+  if (only && unquote) {
+    if (t.ofs_len != 1) return no("on values the output field separator is exactly one byte");
+    if (t.ofs[0] == o.sep) return no("the output field separator cannot be the record separator");
+    if ((int)t.ofs[0] == o.quote) return no("the output field separator cannot be the quote byte");
+    if (o.mode == KX_RECORDS_ESCAPED && (int)t.ofs[0] == o.escape) return no("the output field separator cannot be the escape byte");
+    if (words && t.ofs[0] == 0x09) return no("on the values of words the output field separator cannot be the tab");
+  }
+  if (t.n_items && !named) {
+    kx_field_range u[KX_FIELD_RANGES] = {};
+    uint32_t nu = 0;
+    if (kxFieldItemsUnion(t.items, t.n_items, u, &nu)) return no("the items' union has more than 8 ranges in its normal form");
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int kx_run_records_fd_table(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_records_table* t, int report_fd,
+                                       kx_records_stats* stats) {
+  static const char* const who = "kx_run_records_fd_table";
+  if (!o || !t) return setErr(KX_E_ARG, "null argument");
+  if (const int rc = checkTable(*o, *t, who)) return rc;
+  const bool words = (t->flags & KX_TABLE_WORDS) != 0, unquote = (t->flags & KX_TABLE_UNQUOTE) != 0, only = (t->flags & KX_TABLE_ONLY) != 0;
+  bool named = false;
+  for (uint32_t j = 0; j < t->n_items; ++j) named |= t->items[j].lo == 0;
+  kx_field_range ranges[KX_FIELD_RANGES] = {};
+  uint32_t n_ranges = 0;
+  if (t->n_items && !named) (void)kxFieldItemsUnion(t->items, t->n_items, ranges, &n_ranges);
+  if (!t->header) {   // exactly the entry point the flags name
+    if (!t->n_items) return kx_run_records_fd_opts(p, in_fd, out_fd, o, report_fd, stats);
+    if (t->flags & KX_TABLE_SINGLE) return kx_run_records_fd_fields(p, in_fd, out_fd, o, t->items[0].lo, t->fs, report_fd, stats);
+    if (only)
+      return kx_run_records_fd_field_project(p, in_fd, out_fd, o, t->items, t->n_items, t->fs, t->ofs, t->ofs_len,
+                                             (words ? KX_PROJECT_WORDS : 0u) | (unquote ? KX_PROJECT_UNQUOTE : 0u), report_fd, stats);
+    if (words) return kx_run_records_fd_field_words(p, in_fd, out_fd, o, ranges, n_ranges, unquote ? 1 : 0, report_fd, stats);
+    if (unquote) return kx_run_records_fd_field_values(p, in_fd, out_fd, o, ranges, n_ranges, t->fs, report_fd, stats);
+    return kx_run_records_fd_field_list(p, in_fd, out_fd, o, ranges, n_ranges, t->fs, report_fd, stats);
+  }
+  if (!t->n_items) return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, 0, 0, nullptr, 0, false, false, nullptr, t, who);
+  if (t->flags & KX_TABLE_SINGLE) return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, t->items[0].lo, t->fs, nullptr, 0, false, false, nullptr, t, who);
+  kx_field_project pr{};   // (with names its items are filled in when they are resolved)
+  pr.size = sizeof pr; pr.n_items = t->n_items; pr.ofs_len = t->ofs_len; pr.flags = words ? KX_PROJECT_WORDS : 0u;
+  if (!named) memcpy(pr.items, t->items, sizeof pr.items);
+  memcpy(pr.ofs, t->ofs, sizeof pr.ofs);
+  return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, 0, words ? (uint8_t)0 : t->fs, ranges, n_ranges, unquote, words, only ? &pr : nullptr, t, who);
 }

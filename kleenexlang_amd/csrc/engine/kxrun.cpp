@@ -29,7 +29,10 @@
 // `--only` (with --field) an accepted record writes the outputs of the selected fields alone, in the order the list was WRITTEN
 // (up to 16 items, which may overlap and repeat) and joined by the 0 to 8 bytes of `--ofs=STR` (spelled as --ors; default the --fs
 // byte, or one space with --blanks), then separator and --ors as ever (kx_run_records_fd_field_project; kxParseFieldOrder).  What
-// --field, --fs, --unquote, --blanks, --only and --ofs refuse exits with status 2.
+// --field, --fs, --unquote, --blanks, --only and --ofs refuse exits with status 2.  With `--header[=N]` (with --records; default 1)
+// the first N records are header records — never run, copied, or with --only projected like the records behind them — and the
+// items of --field may be NAMES of cells of header record N (kx_run_records_fd_table; the list's parser is kx_field_names.h): the
+// option's text is then parsed behind the option loop.  A name no cell has ends the run with status 2.
 //
 // BIN = this executable ++ KXP blob ++ libdir ++ trailer (see kexc main.cpp).
 // The engine is loaded with dlopen so that this file carries no HIP dependency.
@@ -47,6 +50,7 @@
 
 #include "../../../include/kxhip.h"
 #include "kx_field_list.h"
+#include "kx_field_names.h"
 
 // The engine's switches are fields of kx_config (include/kxhip.h); the library reads no environment variable for them.  A produced
 // binary keeps honouring the variable names that earlier rounds' scripts use: they are read HERE, once, and mapped onto the struct.
@@ -98,6 +102,7 @@ static void usage(const char* name) {
   fprintf(stdout, "- \"%s --records ... --quote|--escape --field=K|LIST [--fs=F] --unquote\": the program runs on the unquoted value of every selected field; its output is quoted again as it needs.\n", name);
   fprintf(stdout, "- \"%s --records ... --field=K|LIST --blanks [--unquote]\": the fields are the words between runs of spaces and tabs (awk's default); every blank is copied as it is.\n", name);
   fprintf(stdout, "- \"%s --records ... --field=K|LIST [--fs=F | --blanks] [--unquote] --only [--ofs=STR]\": writes only the selected fields' outputs, in the order LIST is written (4,2 or 2,1,2), joined by STR (0 to 8 bytes; default F, or a space with --blanks).\n", name);
+  fprintf(stdout, "- \"%s --records ... --header[=N] [--field=LIST ...]\": the first N records (default 1) are header rows: never run, copied (with --only: projected), and LIST may name columns of row N (id,city or 2,name,5-; \\, is a comma in a name).\n", name);
 }
 
 // --records=SEP, --quote=Q, --escape=E: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
@@ -184,7 +189,8 @@ int main(int argc, char** argv) {
                                          {"chomp", no_argument, 0, 'c'}, {"ors", required_argument, 0, 'o'},
                                          {"field", required_argument, 0, 'f'}, {"fs", required_argument, 0, 'F'},
                                          {"unquote", no_argument, 0, 'u'}, {"blanks", no_argument, 0, 'b'},
-                                         {"only", no_argument, 0, 'y'}, {"ofs", required_argument, 0, 'O'}, {0, 0, 0, 0}};
+                                         {"only", no_argument, 0, 'y'}, {"ofs", required_argument, 0, 'O'},
+                                         {"header", optional_argument, 0, 'H'}, {0, 0, 0, 0}};
   bool timing = false, records = false, quoted = false, escaped = false, sep_given = false, multi = false, chomp = false, ors_given = false;
   uint8_t sep = '\n', quote = '"', escape = '\\', rs[8] = {}, ors[8] = {};
   uint32_t rs_len = 0, ors_len = 0, field = 0;
@@ -198,6 +204,27 @@ int main(int argc, char** argv) {
   uint32_t n_items = 0, ofs_len = 0;
   uint8_t ofs[8] = {};
   long phase = 0, gpus = 0;
+  bool header_given = false, has_names = false;
+  uint32_t header = 1;
+  std::vector<KxFieldNameItem> named;            // --header with a name in --field: the list as written
+  for (int i = 1; i < argc && strcmp(argv[i], "--") != 0; ++i)   // (with --header the text of --field is parsed behind the loop)
+    if (!strcmp(argv[i], "--header") || !strncmp(argv[i], "--header=", 9)) header_given = true;
+  // --field's text without names: null, or the exit status after the message
+  auto parseFieldNumbers = [&](const char* text) -> int {
+    n_ranges = 0; field = 0;
+    if (strpbrk(text, ",-")) {   // a list; one plain number (and what is neither) takes the single-field path below
+      if (const char* why = kxParseFieldList(text, ranges, &n_ranges)) {
+        fprintf(stderr, "Invalid --field: %s (a number from 1 to 4294967295, or a list such as 2,5-7,9-: %s)\n", text, why);
+        return 2;
+      }
+      return 0;
+    }
+    char* end = nullptr;
+    const unsigned long long v = (*text >= '0' && *text <= '9') ? strtoull(text, &end, 10) : 0;
+    if (!end || *end || v < 1 || v > 0xFFFFFFFFull || strlen(text) > 10) { fprintf(stderr, "Invalid --field: %s (a number from 1 to 4294967295)\n", text); return 2; }
+    field = (uint32_t)v;
+    return 0;
+  };
   int c;
   while ((c = getopt_long(argc, argv, "ihtp:", long_options, nullptr)) != -1) {
     switch (c) {
@@ -234,21 +261,18 @@ int main(int argc, char** argv) {
         ors_given = true;
         if (!parseOutputSeparator(optarg, ors, &ors_len)) { fprintf(stderr, "Invalid output record separator: %s\n", optarg); return 1; }
         break;
-      case 'f': {
+      case 'f':
         field_given = true;
         field_text = optarg;
-        n_ranges = 0; field = 0;
-        if (strpbrk(optarg, ",-")) {   // a list; one plain number (and what is neither) takes the single-field path below
-          if (const char* why = kxParseFieldList(optarg, ranges, &n_ranges)) {
-            fprintf(stderr, "Invalid --field: %s (a number from 1 to 4294967295, or a list such as 2,5-7,9-: %s)\n", optarg, why);
-            return 2;
-          }
-          break;
-        }
+        if (!header_given) if (const int bad = parseFieldNumbers(optarg)) return bad;
+        break;
+      case 'H': {
+        header_given = true;
+        if (!optarg) break;
         char* end = nullptr;
         const unsigned long long v = (*optarg >= '0' && *optarg <= '9') ? strtoull(optarg, &end, 10) : 0;
-        if (!end || *end || v < 1 || v > 0xFFFFFFFFull || strlen(optarg) > 10) { fprintf(stderr, "Invalid --field: %s (a number from 1 to 4294967295)\n", optarg); return 2; }
-        field = (uint32_t)v;
+        if (!end || *end || v < 1 || v > 0xFFFFFFFFull || strlen(optarg) > 10) { fprintf(stderr, "Invalid --header: %s (a number from 1 to 4294967295)\n", optarg); return 2; }
+        header = (uint32_t)v;
         break;
       }
       case 'F':
@@ -267,6 +291,15 @@ int main(int argc, char** argv) {
     }
   }
   // (refused before the engine library is loaded)
+  if (header_given && !records) { fprintf(stderr, "%s: --header needs --records\n", argv[0]); return 2; }
+  if (header_given && field_given) {   // --field's text, which may hold names of header cells
+    has_names = kxFieldTextHasName(field_text);
+    if (!has_names) { if (const int bad = parseFieldNumbers(field_text)) return bad; }
+    else if (const char* why = kxParseFieldNames(field_text, &named)) {
+      fprintf(stderr, "Invalid --field: %s (with --header a list of at most 16 numbers, ranges and column names such as 2,name,5-: %s)\n", field_text, why);
+      return 2;
+    }
+  }
   if (records && phase) { fprintf(stderr, "%s: --records cannot be combined with --phase\n", argv[0]); return 1; }
   if (records && gpus) { fprintf(stderr, "%s: --records cannot be combined with --gpus\n", argv[0]); return 1; }
   if (quoted && !records) { fprintf(stderr, "%s: --quote needs --records\n", argv[0]); return 1; }
@@ -295,10 +328,11 @@ int main(int argc, char** argv) {
   if (only && !field_given) { fprintf(stderr, "%s: --only needs --field\n", argv[0]); return 2; }
   if (ofs_given && !only) { fprintf(stderr, "%s: --ofs needs --only\n", argv[0]); return 2; }
   if (only) {   // the list as written (a plain number is the list K-K); its union is what the list's own parse gave
-    if (const char* why = kxParseFieldOrder(field_text, items, &n_items, ranges, &n_ranges)) {
-      fprintf(stderr, "Invalid --field: %s (with --only a list of at most 16 items such as 4,2 or 2,1,2: %s)\n", field_text, why);
-      return 2;
-    }
+    if (!has_names)
+      if (const char* why = kxParseFieldOrder(field_text, items, &n_items, ranges, &n_ranges)) {
+        fprintf(stderr, "Invalid --field: %s (with --only a list of at most 16 items such as 4,2 or 2,1,2: %s)\n", field_text, why);
+        return 2;
+      }
     if (!ofs_given) { ofs[0] = blanks ? (uint8_t)' ' : fsep; ofs_len = 1; }
     if (unquote && ofs_len != 1) { fprintf(stderr, "%s: with --unquote --ofs is exactly one byte\n", argv[0]); return 2; }
     if (unquote && quoted && ofs[0] == quote) { fprintf(stderr, "%s: with --unquote --ofs cannot be the --quote character\n", argv[0]); return 2; }
@@ -306,7 +340,7 @@ int main(int argc, char** argv) {
     if (unquote && (multi ? rs_len == 1 && ofs[0] == rs[0] : ofs[0] == sep)) { fprintf(stderr, "%s: with --unquote --ofs cannot be the record separator\n", argv[0]); return 2; }
     if (unquote && blanks && ofs[0] == '\t') { fprintf(stderr, "%s: with --unquote and --blanks --ofs cannot be the tab\n", argv[0]); return 2; }
   }
-  if ((unquote || blanks) && !n_ranges) { ranges[0] = kx_field_range{field, field}; n_ranges = 1; }   // --field=K on values or words: the list K-K
+  if ((unquote || blanks) && !n_ranges && !has_names) { ranges[0] = kx_field_range{field, field}; n_ranges = 1; }   // --field=K on values or words: the list K-K
   struct timeval t0, t1;
   if (timing) gettimeofday(&t0, nullptr);
 
@@ -332,23 +366,57 @@ int main(int argc, char** argv) {
     decltype(&kx_run_records_fd_field_list) runl = nullptr;
     decltype(&kx_run_records_fd_field_words) runw = nullptr;
     decltype(&kx_run_records_fd_field_project) runp = nullptr;
+    decltype(&kx_run_records_fd_table) runt = nullptr;
     if (!runr) return 1;
-    if (quoted && !(runq = (decltype(runq))engineSymbol(h, argv[0], "kx_run_records_fd_quoted", "--quote needs"))) return 1;
-    if (escaped && !(rune = (decltype(rune))engineSymbol(h, argv[0], "kx_run_records_fd_escaped", "--escape needs"))) return 1;
-    if (multi && !(runm = (decltype(runm))engineSymbol(h, argv[0], "kx_run_records_fd_rs", "--rs needs"))) return 1;
-    if (only && !(runp = (decltype(runp))engineSymbol(h, argv[0], "kx_run_records_fd_field_project", "--only needs"))) return 1;
-    if (field_given && !n_ranges && !(runf = (decltype(runf))engineSymbol(h, argv[0], "kx_run_records_fd_fields", "--field needs"))) return 1;
-    if (blanks && !only && !(runw = (decltype(runw))engineSymbol(h, argv[0], "kx_run_records_fd_field_words", "--blanks needs"))) return 1;
-    if (n_ranges && !unquote && !blanks && !only && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_list", "--field=LIST needs"))) return 1;
-    if (unquote && !blanks && !only && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_values", "--unquote needs"))) return 1;   // (the same signature)
-    if (framing && !(runo = (decltype(runo))engineSymbol(h, argv[0], "kx_run_records_fd_opts", "--chomp and --ors need"))) return 1;
+    if (header_given && !(runt = (decltype(runt))engineSymbol(h, argv[0], "kx_run_records_fd_table", "--header needs"))) return 1;
+    if (!runt && quoted && !(runq = (decltype(runq))engineSymbol(h, argv[0], "kx_run_records_fd_quoted", "--quote needs"))) return 1;
+    if (!runt && escaped && !(rune = (decltype(rune))engineSymbol(h, argv[0], "kx_run_records_fd_escaped", "--escape needs"))) return 1;
+    if (!runt && multi && !(runm = (decltype(runm))engineSymbol(h, argv[0], "kx_run_records_fd_rs", "--rs needs"))) return 1;
+    if (!runt && only && !(runp = (decltype(runp))engineSymbol(h, argv[0], "kx_run_records_fd_field_project", "--only needs"))) return 1;
+    if (!runt && field_given && !n_ranges && !(runf = (decltype(runf))engineSymbol(h, argv[0], "kx_run_records_fd_fields", "--field needs"))) return 1;
+    if (!runt && blanks && !only && !(runw = (decltype(runw))engineSymbol(h, argv[0], "kx_run_records_fd_field_words", "--blanks needs"))) return 1;
+    if (!runt && n_ranges && !unquote && !blanks && !only && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_list", "--field=LIST needs"))) return 1;
+    if (!runt && unquote && !blanks && !only && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_values", "--unquote needs"))) return 1;   // (the same signature)
+    if (!runt && framing && !(runo = (decltype(runo))engineSymbol(h, argv[0], "kx_run_records_fd_opts", "--chomp and --ors need"))) return 1;
     // record mode is where the single-document route is unusable (a third of a millisecond per record): stages with register
     // actions are replayed by the batch kernels unless KX_BATCH_ACTIONS=0 asks for the route
     if (!cfg.batch_actions) cfg.batch_actions = 2;
     kx_program* prog = nullptr;
     if (load(blob.data(), blob.size(), &cfg, &prog)) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 1; }
     kx_records_stats rs_stats;
-    if (framing || field_given) {
+    if (header_given) {   // every combination goes through the one entry point that knows header records
+      kx_records_opts o{};
+      o.size = sizeof o;
+      o.mode = multi ? KX_RECORDS_RS : escaped ? KX_RECORDS_ESCAPED : quoted ? KX_RECORDS_QUOTED : KX_RECORDS_BYTE;
+      o.sep = sep;
+      o.quote = quoted ? (int)quote : -1;
+      o.escape = escaped ? (int)escape : -1;
+      memcpy(o.rs, rs, 8); o.rs_len = rs_len;
+      o.chomp = chomp ? 1u : 0u;
+      memcpy(o.ors, ors, 8); o.ors_len = ors_len;
+      kx_records_table t{};
+      t.size = sizeof t; t.header = header; t.fs = fsep;
+      t.flags = (blanks ? KX_TABLE_WORDS : 0u) | (unquote ? KX_TABLE_UNQUOTE : 0u) | (only ? KX_TABLE_ONLY : 0u);
+      if (has_names) {   // the list as written, its names by index
+        for (const KxFieldNameItem& it : named) {
+          if (it.is_name) {
+            t.items[t.n_items++] = kx_field_range{0u, t.n_names};
+            t.names[t.n_names] = (const uint8_t*)it.name.data(); t.name_len[t.n_names++] = (uint32_t)it.name.size();
+          } else {
+            t.items[t.n_items++] = kx_field_range{(uint32_t)it.lo, it.hi == 1ull << 32 ? 0u : (uint32_t)it.hi};
+          }
+        }
+      } else if (only) {
+        t.n_items = n_items; memcpy(t.items, items, sizeof items);
+      } else if (n_ranges) {   // (a set: its normal form is a list as good as the written one)
+        t.n_items = n_ranges; memcpy(t.items, ranges, sizeof ranges);
+      } else if (field_given) {
+        t.n_items = 1; t.items[0] = kx_field_range{field, field}; t.flags |= KX_TABLE_SINGLE;
+      }
+      if (only) { t.ofs_len = ofs_len; memcpy(t.ofs, ofs, 8); }
+      rc = runt(prog, STDIN_FILENO, STDOUT_FILENO, &o, &t, STDERR_FILENO, &rs_stats);
+      if (rc == KX_E_HEADER) { fprintf(stderr, "%s: %s\n", argv[0], lasterr()); return 2; }
+    } else if (framing || field_given) {
       kx_records_opts o{};
       o.size = sizeof o;
       o.mode = multi ? KX_RECORDS_RS : escaped ? KX_RECORDS_ESCAPED : quoted ? KX_RECORDS_QUOTED : KX_RECORDS_BYTE;

@@ -9,6 +9,7 @@ present, constructing a :class:`Program` raises.
 import contextlib
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 BUILD_DIR = os.path.join(_HERE, "_build")
@@ -48,6 +49,15 @@ class NoFieldError(KleenexError):
     def __init__(self, fields):
         super().__init__("the record has only %d field(s)" % fields)
         self.fields = fields
+
+
+class HeaderError(KleenexError):
+    """Record mode with header=: a name of the field list is no cell of header record N (`name`: its bytes), or the fields the
+    names select have more than 8 ranges in their normal form (`name` is None)."""
+
+    def __init__(self, name, message=None):
+        super().__init__(message or "no cell of the header record is named %r" % (name,))
+        self.name = name
 
 
 class KxStats(ctypes.Structure):
@@ -807,6 +817,147 @@ class KxFieldProject(ctypes.Structure):
 KX_PROJECT_WORDS, KX_PROJECT_UNQUOTE = 1, 2
 
 
+KX_E_HEADER = -6
+KX_TABLE_WORDS, KX_TABLE_UNQUOTE, KX_TABLE_ONLY, KX_TABLE_SINGLE = 1, 2, 4, 8
+FIELD_NAME_MAX = 255
+
+
+class KxRecordsTable(ctypes.Structure):
+    """include/kxhip.h::kx_records_table."""
+    _fields_ = [("size", ctypes.c_uint32), ("header", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("n_items", ctypes.c_uint32),
+                ("items", KxFieldRange * 16), ("n_names", ctypes.c_uint32), ("names", ctypes.c_char_p * 16),
+                ("name_len", ctypes.c_uint32 * 16), ("fs", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3), ("ofs_len", ctypes.c_uint32),
+                ("ofs", ctypes.c_uint8 * 8), ("reserved", ctypes.c_uint32 * 4)]
+
+
+def records_table(header=0, items=(), flags=0, fs=0, ofs=b""):
+    """A KxRecordsTable: `items` as written — ints, (lo, hi) pairs (hi None or 0: open) and bytes names, which go to the table's
+    names in the order of their first appearance.  Nothing is checked here: the library does that."""
+    t = KxRecordsTable(size=ctypes.sizeof(KxRecordsTable), header=header, flags=flags, n_items=len(items), fs=fs, ofs_len=len(ofs))
+    names = []
+    for j, it in enumerate(items[:16]):
+        if isinstance(it, (bytes, bytearray)):
+            if bytes(it) not in names:
+                names.append(bytes(it))
+            t.items[j].lo, t.items[j].hi = 0, names.index(bytes(it))
+        elif isinstance(it, (tuple, list)):
+            t.items[j].lo, t.items[j].hi = it[0], it[1] or 0
+        else:
+            t.items[j].lo = t.items[j].hi = it
+    t.n_names = len(names)
+    for j, name in enumerate(names):
+        t.names[j], t.name_len[j] = name, len(name)
+    t.ofs[:min(len(ofs), 8)] = ofs[:8]
+    return t
+
+
+def parse_field_names(text):
+    """The LIST of `--header --field=LIST` as written → a tuple of ints (K), (lo, hi) pairs (A-B; A- with hi None) and bytes (a
+    NAME), in the order of the text.  The text is cut at the commas that no backslash takes with it (a backslash always takes the
+    next character).  An item made only of digits and '-' is a number item with parse_field_order's rules.  Every other item is a
+    name: its bytes (the text's UTF-8) spelled as themselves or as \\n \\t \\r \\0 \\\\ \\, \\xHH, 1 to 255 of them.  Raises ValueError for
+    what the command line refuses: a bad number item, a bad spelling, a name of more than 255 bytes, more than 16 items, and a list
+    of numbers alone whose union has more than 8 ranges."""
+    if not isinstance(text, str):
+        raise TypeError("field list: a str such as '2,name,5-', not %s" % type(text).__name__)
+    raw, cuts, i = text.encode("utf-8", "surrogateescape"), [], 0
+    while i < len(raw):
+        if raw[i] == 0x5C and i + 1 < len(raw):
+            i += 1
+        elif raw[i] == 0x2C:
+            cuts.append(i)
+        i += 1
+    items, named = [], False
+    for b, e in zip([0] + [c + 1 for c in cuts], cuts + [len(raw)]):
+        item = raw[b:e]
+        if all(c in b"0123456789-" for c in item):
+            (lo, hi), = parse_field_order(item.decode("ascii"))      # (the empty item is refused there)
+            items.append(lo if hi == lo else (lo, hi))
+            continue
+        named, name, k = True, bytearray(), 0
+        while k < len(item):
+            if item[k] != 0x5C:
+                name.append(item[k])
+                k += 1
+                continue
+            c = item[k + 1:k + 2]
+            if c in (b"n", b"t", b"r", b"0", b"\\", b","):
+                name += {b"n": b"\n", b"t": b"\t", b"r": b"\r", b"0": b"\0", b"\\": b"\\", b",": b","}[c]
+                k += 2
+            elif c == b"x" and re.fullmatch(rb"[0-9a-fA-F]{2}", item[k + 2:k + 4]):
+                name.append(int(item[k + 2:k + 4], 16))
+                k += 4
+            else:
+                raise ValueError("field list %r: a backslash in a name starts \\n \\t \\r \\0 \\\\ \\, or \\xHH" % text)
+        if len(name) > FIELD_NAME_MAX:
+            raise ValueError("field list %r: a name has at most %d bytes" % (text, FIELD_NAME_MAX))
+        items.append(bytes(name))
+    if len(items) > FIELD_ITEMS_MAX:
+        raise ValueError("field list %r: %d items, at most %d" % (text, len(items), FIELD_ITEMS_MAX))
+    if not named:
+        parse_field_order(text)
+    return tuple(items)
+
+
+def header_names_model(body, fs, quote=None, escape=None, blanks=False, first=False):
+    """The names of the cells of a header record's `body` (the record without its separator) in pure Python — the normative model
+    of what `--header` resolves names against.  The cells lie between the live `fs` bytes, as field_records_model has them (the
+    empty body has one empty cell); with `blanks` (and fs None) they are the body's words, as blank_field_list_records_model has
+    them.  A cell's name is its bytes; with a `quote` or an `escape` byte it is the cell's unquote_field_model value.  With `first`
+    (the record is the stream's first) a leading EF BB BF is cut off before anything else."""
+    if not isinstance(body, (bytes, bytearray, memoryview)):
+        raise TypeError("header_names_model: body must be bytes, not %s" % type(body).__name__)
+    for name, v in (("blanks", blanks), ("first", first)):
+        if not isinstance(v, bool):
+            raise TypeError("header_names_model: %s must be True or False, not %s" % (name, type(v).__name__))
+    body = bytes(body)
+    if first and body[:3] == b"\xef\xbb\xbf":
+        body = body[3:]
+    if blanks:
+        if fs is not None:
+            raise ValueError("header_names_model: blanks= cannot be combined with an fs")
+        rec = blank_field_list_records_model(body, [0, len(body)], 0, False, [(1, None)], quote, escape)[0]
+    else:
+        rec = field_list_records_model(body, [0, len(body)], 0, False, [(1, None)], fs, quote, escape)[0]
+    cells = [] if isinstance(rec, int) else [v for _, v in rec[1]]
+    if quote is None and escape is None:
+        return cells
+    return [unquote_field_model(c, quote, escape) for c in cells]
+
+
+def resolve_field_names(items, names):
+    """`items` — ints, (lo, hi) pairs and bytes names, as parse_field_names gives them — against the cell `names` of the header
+    record → the items with every name replaced by the number (from 1) of the lowest-numbered cell that has it.  Raises HeaderError
+    for a name no cell has."""
+    names = [bytes(n) for n in names]
+    out = []
+    for it in items:
+        if isinstance(it, (bytes, bytearray)):
+            if bytes(it) not in names:
+                raise HeaderError(bytes(it))
+            it = names.index(bytes(it)) + 1
+        out.append(it)
+    return out
+
+
+def _check_header(what, header, fields):
+    """The `header=` keyword of record mode: an int in [0, 2^32); names in `fields` only with header >= 1, each 1 to 255 bytes,
+    in a list of at most 16 items → (header, whether `fields` holds a name)."""
+    if isinstance(header, bool) or not isinstance(header, int):
+        raise TypeError("%s: header must be an int, not %s" % (what, type(header).__name__))
+    if not 0 <= header < 1 << 32:
+        raise ValueError("%s: header: %d is not in [0, 2^32)" % (what, header))
+    names = [it for it in fields if isinstance(it, (bytes, bytearray))] if isinstance(fields, (tuple, list)) else []
+    if names and not header:
+        raise ValueError("%s: names in fields= need header >= 1" % what)
+    if names and len(fields) > FIELD_ITEMS_MAX:
+        raise ValueError("%s: fields: %d items, at most %d in a list with a name" % (what, len(fields), FIELD_ITEMS_MAX))
+    for n in names:
+        if not 1 <= len(n) <= FIELD_NAME_MAX:
+            raise ValueError("%s: fields: a name has 1 to %d bytes, not %d" % (what, FIELD_NAME_MAX, len(n)))
+    return header, bool(names)
+
+
 def _field_item_array(items):
     """Items as written → (KxFieldRange * 16, n_items)."""
     a = (KxFieldRange * 16)()
@@ -1138,6 +1289,9 @@ def load_engine():
         lib.kx_run_records_fd_field_project.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.POINTER(KxFieldRange),
                                                         u32, ctypes.c_uint8, ctypes.c_char_p, u32, u32, ctypes.c_int,
                                                         ctypes.POINTER(KxRecordsStats)]
+        lib.kx_run_batch_field_header.argtypes = lib.kx_run_batch_field_project.argtypes
+        lib.kx_run_records_fd_table.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.POINTER(KxRecordsTable),
+                                                ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
         lib.kx_run_records_fd_fields.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), u32, ctypes.c_uint8,
                                                  ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
         lib.kx_run_records_fd_opts.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.c_int,
@@ -1613,12 +1767,13 @@ class Program:
             frame.suffix[:len(suffix)] = bytes(suffix)
         return self._run_batch_call("run_batch_tensor", values, offsets, out, frame, None)
 
-    def _run_batch_call(self, what, values, offsets, out, frame, fields, codec=None, words=False, proj=None):
+    def _run_batch_call(self, what, values, offsets, out, frame, fields, codec=None, words=False, proj=None, identity=False):
         """The device part of run_batch_tensor (`frame`: a KxBatchFrame or None), run_batch_fields_tensor (`fields`: a
         KxBatchFields), run_batch_field_list_tensor (`fields`: a KxBatchFieldList, which adds the fail_field tensor to the
         result), run_batch_field_values_tensor (the same with `codec`: a KxFieldCodec) and run_batch_field_words_tensor (`words`;
         `codec` a KxFieldCodec or None) and run_batch_field_project_tensor (`proj`: a KxFieldProject, whose flags say whether the
-        fields are words): the checks that need the tensors' device, the buffers, the size query and the call."""
+        fields are words; with `identity` kx_run_batch_field_header): the checks that need the tensors' device, the buffers, the size
+        query and the call."""
         import torch
         if not values.is_cuda:
             raise EngineError("%s: values must be on a HIP device (there is no CPU fallback)" % what)
@@ -1644,11 +1799,11 @@ class Program:
             bptr = ctypes.c_void_p(buf.data_ptr() if buf is not None and buf.numel() else None)
             bcap = buf.numel() if buf is not None else 0
             if proj is not None:
-                rc = self._lib.kx_run_batch_field_project(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
-                                                          ctypes.byref(fields), ctypes.byref(codec) if codec is not None else None,
-                                                          ctypes.byref(proj), bptr, bcap, ctypes.c_void_p(out_off.data_ptr()),
-                                                          ctypes.c_void_p(docs.data_ptr()), ctypes.c_void_p(ffield.data_ptr()),
-                                                          ctypes.byref(ol), ctypes.byref(st), ctypes.c_void_p(stream))
+                entry = self._lib.kx_run_batch_field_header if identity else self._lib.kx_run_batch_field_project
+                rc = entry(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
+                           ctypes.byref(fields), ctypes.byref(codec) if codec is not None else None, ctypes.byref(proj), bptr, bcap,
+                           ctypes.c_void_p(out_off.data_ptr()), ctypes.c_void_p(docs.data_ptr()), ctypes.c_void_p(ffield.data_ptr()),
+                           ctypes.byref(ol), ctypes.byref(st), ctypes.c_void_p(stream))
             elif words:
                 rc = self._lib.kx_run_batch_field_words(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
                                                         ctypes.byref(fields), ctypes.byref(codec) if codec is not None else None, bptr,
@@ -1823,8 +1978,17 @@ class Program:
         spec.suffix[:len(suffix)] = bytes(suffix)
         return self._run_batch_call(what, values, offsets, out, None, spec, codec, words=True)
 
+    def run_batch_field_header_tensor(self, values, offsets, items, ofs, fs=b"\t", blanks=False, quote=None, escape=None, unquote=False,
+                                      special=b"\n", sep_len=0, last_whole=False, keep_sep=True, suffix=b"", out=None):
+        """run_batch_field_project_tensor with the identity in the program's place (kx_run_batch_field_header): the route of a
+        header record under `only=`.  Every record with enough fields writes its selected fields themselves — with `unquote` the
+        spelling of each one's value, requote_field_model(unquote_field_model(cell), …) — in the written order; no record is
+        rejected by the program."""
+        return self.run_batch_field_project_tensor(values, offsets, items, ofs, fs, blanks, quote, escape, unquote, special, sep_len,
+                                                   last_whole, keep_sep, suffix, out, _identity=True)
+
     def run_batch_field_project_tensor(self, values, offsets, items, ofs, fs=b"\t", blanks=False, quote=None, escape=None, unquote=False,
-                                       special=b"\n", sep_len=0, last_whole=False, keep_sep=True, suffix=b"", out=None):
+                                       special=b"\n", sep_len=0, last_whole=False, keep_sep=True, suffix=b"", out=None, _identity=False):
         """Field mode, projected (kx_run_batch_field_project, project_records_model): the program runs once on every field of the
         union of `items` (a parse_field_order result, or 1 to 16 ints and (lo, hi) pairs in any order), as
         run_batch_field_list_tensor runs it — with `blanks` on the words, as run_batch_field_words_tensor (`fs` is then not used);
@@ -1832,7 +1996,7 @@ class Program:
         `unquote` their spellings, which protect the one byte of `ofs` in place of `fs`), item by item in the written order, joined
         by the 0 to 8 bytes `ofs`, then separator and suffix as there.  Returns the six tensors of run_batch_field_list_tensor;
         fail_field is the lowest rejected field number whatever the order."""
-        what = "run_batch_field_project_tensor"
+        what = "run_batch_field_header_tensor" if _identity else "run_batch_field_project_tensor"
         _check_batch_args(values, offsets)
         (items, ranges), sep_len, ofs = _check_field_items(items), _check_sep_len(sep_len), _check_ofs(ofs)
         for name, v in (("blanks", blanks), ("unquote", unquote), ("last_whole", last_whole), ("keep_sep", keep_sep)):
@@ -1867,7 +2031,7 @@ class Program:
         proj = KxFieldProject(size=ctypes.sizeof(KxFieldProject), n_items=ni, items=iarr, ofs_len=len(ofs),
                               flags=KX_PROJECT_WORDS if blanks else 0)
         proj.ofs[:len(ofs)] = ofs
-        return self._run_batch_call(what, values, offsets, out, None, spec, codec, proj=proj)
+        return self._run_batch_call(what, values, offsets, out, None, spec, codec, proj=proj, identity=_identity)
 
     def fields_kernel_stats(self):
         """kx_fields_stats: HIP-event times of field mode's own kernels, summed over this program's calls (collect_timing)."""
@@ -1977,7 +2141,7 @@ class Program:
         return rs
 
     def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None, batch_actions=True, rs=None, chomp=False, ors=b"",
-                    field=None, fs=None, fields=None, unquote=False, blanks=False, only=False, ofs=None):
+                    field=None, fs=None, fields=None, unquote=False, blanks=False, only=False, ofs=None, header=0):
         """Record mode on bytes: every record of `data` (split after each `sep` byte, kx_split_records on the device) is a
         whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage).  With a `quote` byte
         a separator inside quotes ends no record (kx_split_records_quoted from parity 0).  With an `escape` byte an escaped
@@ -2000,9 +2164,18 @@ class Program:
         `field=K` is then the list K-K, and a record without any word gives NoFieldError(0).  With `only` (with `field` or `fields`)
         an accepted record gives the outputs of its selected fields alone, in the order the `fields` sequence has them — items
         may overlap and repeat — joined by the 0 to 8 bytes `ofs` (default `fs`, or one space with `blanks`), then separator and
-        `ors` as ever (kx_run_batch_field_project, project_records_model); with `unquote` the spellings protect `ofs`, one byte."""
+        `ors` as ever (kx_run_batch_field_project, project_records_model); with `unquote` the spellings protect `ofs`, one byte.
+        With `header` = N the first N records are header records: the program never runs on them, and the list holds their bytes
+        in their places — body, separator unless `chomp`, `ors`; with `only` their projection (kx_run_batch_field_header), or a
+        NoFieldError.  `fields` may then hold bytes NAMES, resolved against the cells of record N (header_names_model,
+        resolve_field_names): a name no cell has raises HeaderError; data with fewer than N records resolves nothing (under `only`
+        with names its records then give b"")."""
         if not isinstance(data, (bytes, bytearray, memoryview)):
             raise TypeError("run_records: data must be bytes, not %s" % type(data).__name__)
+        header, named = _check_header("run_records", header, fields)
+        written = list(fields) if named else None
+        if named:                                        # (a placeholder for the checks; the numbers come with record N)
+            fields = [1 if isinstance(it, (bytes, bytearray)) else it for it in fields]
         chomp, ors = _check_chomp(chomp), _check_ors(ors)
         items, ofs = self._check_only("run_records", only, ofs, field, fields, fs, blanks)
         if items is not None:
@@ -2048,39 +2221,71 @@ class Program:
             last = data[int(offs[-2]):] if (chomp or field is not None or fields is not None) and offs.numel() > 1 else b""
             tail = bool(last) and len(last) not in model(last + b"\0")[:-1]
         trim = (len(rs) if rs is not None else 1) if chomp else 0
-        ffield = None
+
+        def unpack(res):
+            out, ooff, status, fpos, fstage = res[:5]
+            torch.cuda.synchronize(dev)
+            ob = out.cpu().numpy().tobytes()
+            ooff, status, fpos, fstage = ooff.tolist(), status.tolist(), fpos.tolist(), fstage.tolist()
+            ffield = [None] * len(status) if len(res) < 6 else res[5].tolist()
+            return [NoFieldError(fpos[i]) if status[i] == 2 else MatchError(fpos[i], fstage[i], ffield[i]) if status[i] else ob[ooff[i]:ooff[i + 1]]
+                    for i in range(len(status))]
+
+        head, nrec, sep_len = [], offs.numel() - 1, len(rs) if rs is not None else 1
+        nh = min(header, nrec)
+        if nh:                                           # the header records
+            ho = offs[:nh + 1].tolist()
+            if named and nrec >= header:
+                cut = 0 if tail and header == nrec else sep_len
+                cells = header_names_model(data[ho[-2]:ho[-1] - cut], fs, quote, escape, blanks, header == 1)
+                resolved = resolve_field_names(written, cells)
+                try:
+                    if items is not None:
+                        items, fields = _check_field_items(resolved)
+                    else:
+                        fields = _check_field_ranges(resolved)
+                except ValueError as ex:
+                    raise HeaderError(None, str(ex))
+            if items is not None and named and nrec < header:
+                head = [b""] * nh
+            elif items is not None:
+                head = unpack(self.run_batch_field_header_tensor(
+                    v, offs[:nh + 1], items, ofs, fs, blanks, quote, escape, unquote=unquote, special=sep_byte, sep_len=sep_len,
+                    last_whole=bool(tail and nh == nrec), keep_sep=not chomp, suffix=ors))
+            else:
+                for i in range(nh):
+                    cut = 0 if tail and i == nrec - 1 else sep_len
+                    head.append(data[ho[i]:ho[i + 1] - cut] + (b"" if chomp else data[ho[i + 1] - cut:ho[i + 1]]) + ors)
+            if nh == nrec:
+                return head
+            offs = offs[nh:]
         with self._batch_actions_for_call(batch_actions):
             if items is not None:
-                out, ooff, status, fpos, fstage, ffield = self.run_batch_field_project_tensor(
+                res = self.run_batch_field_project_tensor(
                     v, offs, items, ofs, fs, blanks, quote, escape, unquote=unquote, special=sep_byte,
                     sep_len=len(rs) if rs is not None else 1, last_whole=bool(tail and data), keep_sep=not chomp, suffix=ors)
             elif blanks:
-                out, ooff, status, fpos, fstage, ffield = self.run_batch_field_words_tensor(
+                res = self.run_batch_field_words_tensor(
                     v, offs, fields, quote, escape, unquote=unquote, special=sep_byte, sep_len=len(rs) if rs is not None else 1,
                     last_whole=bool(tail and data), keep_sep=not chomp, suffix=ors)
             elif unquote:
-                out, ooff, status, fpos, fstage, ffield = self.run_batch_field_values_tensor(
+                res = self.run_batch_field_values_tensor(
                     v, offs, fields, fs, quote, escape, special=sep_byte, sep_len=1, last_whole=bool(tail and data), keep_sep=not chomp,
                     suffix=ors)
             elif fields is not None:
-                out, ooff, status, fpos, fstage, ffield = self.run_batch_field_list_tensor(
+                res = self.run_batch_field_list_tensor(
                     v, offs, fields, fs, quote, escape, sep_len=len(rs) if rs is not None else 1, last_whole=bool(tail and data),
                     keep_sep=not chomp, suffix=ors)
             elif field is not None:
-                out, ooff, status, fpos, fstage = self.run_batch_fields_tensor(
+                res = self.run_batch_fields_tensor(
                     v, offs, field, fs, quote, escape, sep_len=len(rs) if rs is not None else 1, last_whole=bool(tail and data),
                     keep_sep=not chomp, suffix=ors)
             else:
-                out, ooff, status, fpos, fstage = self.run_batch_tensor(v, offs, trim=trim, last_whole=bool(trim and tail and data), suffix=ors)
-        torch.cuda.synchronize(dev)
-        ob = out.cpu().numpy().tobytes()
-        ooff, status, fpos, fstage = ooff.tolist(), status.tolist(), fpos.tolist(), fstage.tolist()
-        ffield = [None] * len(status) if ffield is None else ffield.tolist()
-        return [NoFieldError(fpos[i]) if status[i] == 2 else MatchError(fpos[i], fstage[i], ffield[i]) if status[i] else ob[ooff[i]:ooff[i + 1]]
-                for i in range(len(status))]
+                res = self.run_batch_tensor(v, offs, trim=trim, last_whole=bool(trim and tail and data), suffix=ors)
+        return head + unpack(res)
 
     def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None, batch_actions=True, rs=None, chomp=False,
-                       ors=b"", field=None, fs=None, fields=None, unquote=False, blanks=False, only=False, ofs=None):
+                       ors=b"", field=None, fs=None, fields=None, unquote=False, blanks=False, only=False, ofs=None, header=0):
         """kx_run_records_fd: the stream on in_fd in record mode, outputs to out_fd, one line per rejected record to report_fd
         (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected.  With a `quote`
         byte, kx_run_records_fd_quoted: a separator inside quotes ends no record.  With an `escape` byte,
@@ -2093,7 +2298,13 @@ class Program:
         list, and a record with a rejected field is reported once, with the field's number.  With `unquote` (as in run_records),
         kx_run_records_fd_field_values: the program runs on the values of the selected fields, which are spelled again behind it.
         With `blanks` (as in run_records), kx_run_records_fd_field_words: the fields are the words between live spaces and tabs.
-        With `only` and `ofs` (as in run_records), kx_run_records_fd_field_project: only the selected fields' outputs are written."""
+        With `only` and `ofs` (as in run_records), kx_run_records_fd_field_project: only the selected fields' outputs are written.
+        With `header` = N >= 1, kx_run_records_fd_table: the first N records are header records, and `fields` may hold bytes names of
+        the cells of record N; a name no cell has raises EngineError (KX_E_HEADER) with the library's message."""
+        header, named = _check_header("run_records_fd", header, fields)
+        written = list(fields) if named else None
+        if named:                                        # (a placeholder for the checks; the library resolves the names)
+            fields = [1 if isinstance(it, (bytes, bytearray)) else it for it in fields]
         items, ofs = self._check_only("run_records_fd", only, ofs, field, fields, fs, blanks)
         if items is not None:
             field, fields = None, list(items)
@@ -2120,7 +2331,7 @@ class Program:
             f = _check_fs(fs, quote, escape, sep if rs is None else rs if len(rs) == 1 else None)
         st = KxRecordsStats()
         with self._batch_actions_for_call(batch_actions):
-            if chomp or ors or field is not None or fields is not None:   # the framing: only kx_run_records_fd_opts (and _fields, _field_list) has it
+            if chomp or ors or field is not None or fields is not None or header:   # the framing: only kx_run_records_fd_opts (and _fields, _field_list) has it
                 o = KxRecordsOpts(size=ctypes.sizeof(KxRecordsOpts), mode=mode, sep=s, quote=qi, escape=-1 if e is None else e,
                                   rs_len=len(rs or b""), chomp=1 if chomp else 0, ors_len=len(ors))
                 o.rs[:o.rs_len] = rs or b""
@@ -2139,6 +2350,13 @@ class Program:
                         iarr, ni = _field_item_array(items)
                         name, args = "kx_run_records_fd_field_project", (ctypes.byref(o), iarr, ni, f, ofs, len(ofs),
                                                                          (KX_PROJECT_WORDS if blanks else 0) | (KX_PROJECT_UNQUOTE if unquote else 0))
+                if header:                               # one entry point for every combination
+                    tflags = (KX_TABLE_WORDS if blanks else 0) | (KX_TABLE_UNQUOTE if unquote else 0) | (KX_TABLE_ONLY if items is not None else 0)
+                    titems = written if named else items if items is not None else fields if fields is not None else []
+                    if field is not None:
+                        titems, tflags = [field], KX_TABLE_SINGLE
+                    table = records_table(header, list(titems), tflags, f, ofs or b"")
+                    name, args = "kx_run_records_fd_table", (ctypes.byref(o), ctypes.byref(table))
             else:                                        # the mode's own entry point
                 name, args = (("kx_run_records_fd", (s,)), ("kx_run_records_fd_quoted", (s, q)), ("kx_run_records_fd_escaped", (s, qi, e)),
                               ("kx_run_records_fd_rs", (rs, len(rs or b""))))[mode]
