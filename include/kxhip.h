@@ -652,6 +652,68 @@ int kx_run_batch_field_header(kx_program* prog, const void* d_in, const uint64_t
                               uint64_t* d_out_off, kx_batch_doc* d_docs, uint32_t* d_fail_field, size_t* out_len, kx_batch_stats* stats,
                               void* stream);
 
+/* ---- field mode by key: the fields are key=value pairs, and the program runs on the values of the listed keys ----------------------
+ * (`BIN --records … --field=LIST --keys[=C]`; the normative text is host.keyed_records_model.)  kx_run_batch_field_keys is
+ * kx_run_batch_field_list — with KX_KEYS_WORDS kx_run_batch_field_words, with a codec kx_run_batch_field_values, with `proj`
+ * kx_run_batch_field_project — in everything not said here: the records, their bodies, how a body is cut into fields (the live
+ * `fs` bytes; with KX_KEYS_WORDS the words between live blanks), sep_len, last_whole, keep_sep and the suffix, the codec's value
+ * and spelling rules, return codes, KX_E_CAPACITY and the size query, and the statistics.  `list` carries that framing; its
+ * n_ranges MUST be 0 (with KX_KEYS_WORDS its fs too).
+ *   Inside a field the KEY is the bytes before the field's first live `kv` byte — live under the rule that makes an fs byte live,
+ * with the record's running state — and the VALUE everything behind that byte up to the field's end; it may be empty.  A field
+ * without a live kv byte has no key; an empty key matches nothing; keys are compared as raw bytes, quotes and escapes included.
+ * Per record each name selects the FIRST field that has it for a key; later fields with that key are bytes like any other.
+ *   The selected values are the record's documents, in address order: each is run as a whole input of its own (with a codec its
+ * value, host.unquote_field_model; fail_pos counts inside it).
+ *   A record that lacks a name whose bit is not set in optional_mask: its output range is empty, d_docs[i] = {the 16-bit mask of
+ *     the names it has, 2, 0}, d_fail_field[i] = 1 + the index of the first such name; the program runs on none of its values.
+ *   A record with a rejected value: its output range is empty, d_docs[i] = {fail_pos, 1, fail_stage} of the rejected value at the
+ *     lowest address, d_fail_field[i] = 1 + the index of its name.
+ *   Any other record is accepted, d_docs[i] = {0, 0, 0}, d_fail_field[i] = 0: its output is its body with each selected value
+ *     replaced (key and kv byte are copied) + its own separator (keep_sep) + suffix; a record that holds none of the names — all
+ *     of them optional — is written unchanged.  With `proj`: for each item in written order — proj->items[t] = {0, name index} —
+ *     the output of that name's value, joined by ofs; an optional name the record lacks writes nothing and no ofs, and a record
+ *     without any output writes its separator and the suffix alone.
+ * `names` are the DISTINCT names in the order the list was written, so that "the first name it lacks" is the lowest index; with
+ * `proj` every name index an item holds is below n_names.  KX_E_ARG besides those calls', before any device work: a null `keys` or
+ * a wrong `size`; n_names = 0 or > 16; a null name, one of 0 or more than 255 bytes, two equal names; optional_mask bits at or
+ * above n_names; unknown flag bits; a non-zero reserved word; list->n_ranges != 0; kv equal to fs (KX_KEYS_WORDS: a blank), the
+ * quote or the escape byte; a name that holds kv or fs (KX_KEYS_WORDS: a blank); with `proj` a wrong size, 0 or more than 16
+ * items, an item that is no {0, index < n_names}, ofs_len > 8, and with a codec too an ofs that is not one byte or equals the
+ * quote, the escape or a special byte.  Beside kx_run_batch_field_list's workspace the library holds 4 144 bytes for the names'
+ * table, a byte per document and with `proj` 16 bytes per record. */
+#define KX_KEYS_WORDS 1u        /* the fields are the body's words (list->fs must be 0) */
+#define KX_KEYS_UNQUOTE 2u      /* kx_run_records_fd_field_keys only: the program runs on the values' values (a codec with o->sep) */
+#define KX_KEYS_ONLY 4u         /* kx_run_records_fd_field_keys only: items and ofs are a projection */
+typedef struct kx_field_keys {
+  uint32_t size;              /* sizeof(kx_field_keys) */
+  uint32_t n_names;           /* 1 to 16 */
+  const uint8_t* names[16];   /* distinct, in written order */
+  uint32_t name_len[16];      /* 1 to 255 */
+  uint32_t optional_mask;     /* bit t: a record may lack names[t] */
+  uint8_t kv;                 /* the key separator C */
+  uint8_t pad[3];             /* must be 0 */
+  uint32_t flags;             /* KX_KEYS_WORDS */
+  uint32_t reserved[4];       /* must be 0 */
+} kx_field_keys;
+int kx_run_batch_field_keys(kx_program* prog, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* list,
+                            const kx_field_keys* keys, const kx_field_codec* codec /* or NULL */, const kx_field_project* proj /* or NULL */,
+                            void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs, uint32_t* d_fail_field, size_t* out_len,
+                            kx_batch_stats* stats, void* stream);
+
+/* kx_run_records_fd_field_list by key (`BIN --records … --field=LIST --keys[=C] [--fs=F | --blanks] [--unquote] [--only
+ * [--ofs=STR]]`): every record goes through kx_run_batch_field_keys.  keys->flags: KX_KEYS_WORDS (`fs` is not used),
+ * KX_KEYS_UNQUOTE (a codec whose special byte is o->sep) and KX_KEYS_ONLY (a projection of items[0, n_items), each an index into
+ * keys->names, joined by ofs[0, ofs_len); without it items may be NULL).  A record that lacks a required name reports "Record R
+ * has no field NAME!", NAME the first such name; a record with a rejected value reports once, "Match error at input symbol S in
+ * field NAME of record R!"; both write nothing and count in records_rejected.  NAME is printed with its bytes outside 0x20 to
+ * 0x7E as \xHH.  KX_E_ARG: kx_run_records_fd_field_list's (with KX_KEYS_WORDS _field_words's, with KX_KEYS_UNQUOTE
+ * _field_values's, with KX_KEYS_ONLY _field_project's for the ofs), kx_run_batch_field_keys's for `keys`, and a kv or a name
+ * byte equal to the one-byte record separator. */
+int kx_run_records_fd_field_keys(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_field_keys* keys, uint8_t fs,
+                                 const uint32_t* items, uint32_t n_items, const uint8_t* ofs, uint32_t ofs_len, int report_fd,
+                                 kx_records_stats* stats);
+
 /* ---- sharded execution: one contiguous shard of the input per GPU -------------
  * Per stage and per rank:
  *   kx_shard_begin → kx_shard_forward → [exchange kx_fwd_summary] → kx_shard_fix_head

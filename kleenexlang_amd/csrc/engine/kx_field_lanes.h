@@ -1,7 +1,8 @@
 // kx_field_lanes.h — per-lane bodies of field mode's kernels that also compile as plain C++: the helpers the splice kernels share
 // (fld_find, fld_put), the walks of the range table and the result of a record from its documents' (k_flsplen and k_fpsplen), and
 // the two lane bodies of the projection (`--only`: k_fpsplen, k_fpsplice in kx_field_project.inc, which are thin grid-stride loops
-// over them).  Included by kx_fields.inc inside kx_engine.hip, where KX_LANE is `__device__ __forceinline__`, and by
+// over them), and the status rule of keyed runs (KVSpec, kv_status: `--keys`, kx_field_keys.inc, whose projection runs the same two
+// lane bodies with a KVSpec).  Included by kx_fields.inc inside kx_engine.hip, where KX_LANE is `__device__ __forceinline__`, and by
 // tests/native/project_lanes.cpp, a stand-alone host program that runs the same text one lane at a time under a sanitizer.
 // Needs kx_batch_doc (include/kxhip.h) from the including file; reads no other engine type.
 #pragma once
@@ -68,13 +69,46 @@ KX_LANE kx_batch_doc fl_status(const unsigned long long* __restrict__ rng, unsig
   return r;
 }
 
+// ---- keyed runs (`--keys`, kx_field_keys.inc): a record's documents are the values of the first fields whose keys are the listed
+// names, in address order; document t is the value of name dkey[t].
+
+// what the kernels know of a kx_field_keys.  The names are a table in device memory as the ranges are (an indexed kernel argument
+// would go through scratch): 16 lengths and 16 offsets of 16 bits each, then the names' bytes at tab + 64 + offset.
+struct KVSpec {
+  const uint8_t* tab;    // the names
+  const uint8_t* dkey;   // per document: the index of its name (k_kvlocate writes it)
+  const uint8_t* kdoc;   // with a projection, per record 16 bytes: the record-relative document of name t, or 0xFF
+  uint32_t all, req;     // bit t: name t is listed; it is required
+  uint32_t kv;           // the key separator C
+};
+
+// fl_status of a keyed run: nf[i] is the mask of the names record i has.  Without a document the record is accepted if it lacks no
+// required name — else {names found, 2, 0}, K = 1 + the lowest required name it lacks (the names are numbered as written); else the
+// first document with a non-zero status gives the record's, K = 1 + its name
+KX_LANE kx_batch_doc kv_status(const KVSpec& V, unsigned long long i, unsigned long long da, unsigned long long db,
+                               const unsigned long long* __restrict__ nf, const kx_batch_doc* __restrict__ drec, unsigned long long& K) {
+  kx_batch_doc r{0, 0u, 0u};
+  K = 0;
+  if (da == db) {
+    const uint32_t miss = V.req & ~(uint32_t)nf[i];
+    if (miss) { r = kx_batch_doc{nf[i], 2u, 0u}; K = 1ull + (unsigned long long)__builtin_ctz(miss); }
+  } else {
+    unsigned long long t = da;
+    while (t < db && drec[t].status == 0) ++t;                  // the rejected value at the lowest address
+    if (t < db) { r = drec[t]; K = 1ull + V.dkey[t]; }
+  }
+  return r;
+}
+
 // ---- the projection (`--only`): an accepted record writes, item by item as the list was written, the outputs of the item's fields,
 // every two consecutive outputs joined by OFS, then the kept separator, then the suffix.  An item's fields are consecutive members
 // of S, so consecutive documents: item t of a record with the documents da .. da + m - 1 begins at document a = da + rank (the
 // members of S below the item's lo) and has c of them: hi - lo + 1, or what the record has of them.  Only an item inside S's
 // open range can have fewer, or none (3-,9-10 on a record of 5 fields: need is 3): the range's documents are the record's last,
 // so c = min(hi - lo + 1, m - rank) and the fields found are not needed.  An item without a field writes nothing, no OFS either;
-// a record with `need` fields has at least one output (the item that gave the open range its lo, or any closed one).
+// a record with `need` fields has at least one output (the item that gave the open range its lo, or any closed one).  In a keyed
+// run (`kv` set) item t is a name, P.itm[t] its index: its one document is kdoc[16 i + index], and an optional name the record
+// lacks has none — an accepted record may then have no output at all, and writes its separator and the suffix alone.
 
 // what k_fpsplen and k_fpsplice know of a kx_field_project and of the list's framing.  The items are a table in device memory as
 // the ranges are (an indexed kernel argument would go through scratch): rank[0..15] then size[0..15], size = hi - lo + 1, or
@@ -92,9 +126,17 @@ KX_LANE unsigned long long fp_body_end(const FPSpec& P, unsigned long long e, un
   return e - (i == P.whole ? 0ull : P.sep_len);
 }
 
-// item t of a record with m documents from da: its first document, and how many (0: a is not a document of the record's)
-KX_LANE void fp_item(const FPSpec& P, uint32_t t, unsigned long long da, unsigned long long m, unsigned long long& a, unsigned long long& c) {
+// item t of a record with m documents from da: its first document, and how many (0: a is not a document of the record's).  krow:
+// null, or in a keyed run the record's 16 bytes of kdoc (c is then 0 or 1)
+KX_LANE void fp_item(const FPSpec& P, uint32_t t, unsigned long long da, unsigned long long m, unsigned long long& a, unsigned long long& c,
+                     const uint8_t* __restrict__ krow = nullptr) {
   const unsigned long long rk = P.itm[t], size = P.itm[16 + t];
+  if (krow) {
+    const uint32_t x = m ? krow[rk] : 0xFFu;                    // (a record without a document has no row)
+    a = da + x;
+    c = x != 0xFFu ? 1ull : 0ull;
+    return;
+  }
   a = da + rk;
   c = rk >= m ? 0ull : size < m - rk ? size : m - rk;
 }
@@ -103,19 +145,20 @@ KX_LANE void fp_item(const FPSpec& P, uint32_t t, unsigned long long da, unsigne
 KX_LANE unsigned long long fp_splen_lane(const FPSpec& P, const unsigned long long* __restrict__ off, unsigned long long i,
                                          const unsigned long long* __restrict__ d0, const unsigned long long* __restrict__ nf,
                                          const unsigned long long* __restrict__ poff, const kx_batch_doc* __restrict__ drec,
-                                         kx_batch_doc* rec, unsigned long long* K) {
+                                         kx_batch_doc* rec, unsigned long long* K, const KVSpec* kv = nullptr) {
   const unsigned long long da = d0[i], db = d0[i + 1];
-  *rec = fl_status(P.rng, i, da, db, nf, drec, *K);
+  *rec = kv ? kv_status(*kv, i, da, db, nf, drec, *K) : fl_status(P.rng, i, da, db, nf, drec, *K);
   if (rec->status != 0) return 0;
   const unsigned long long e = off[i + 1], be = fp_body_end(P, e, i);
-  unsigned long long len = (P.keep ? e - be : 0ull) + P.sfx_len, w = 0;   // w: the outputs written (at least one)
+  unsigned long long len = (P.keep ? e - be : 0ull) + P.sfx_len, w = 0;   // w: the outputs written (at least one; keyed: or none)
+  const uint8_t* const krow = kv ? kv->kdoc + 16 * i : nullptr;
   for (uint32_t t = 0; t < P.n_items; ++t) {
     unsigned long long a, c;
-    fp_item(P, t, da, db - da, a, c);
+    fp_item(P, t, da, db - da, a, c, krow);
     if (c) len += poff[a + c] - poff[a];
     w += c;
   }
-  return len + (w - 1) * P.ofs_len;
+  return len + (w ? (w - 1) * P.ofs_len : 0ull);
 }
 
 // k_fpsplice's lane: granule g of out[0, total) as it lies in memory (any alignment; `lead` bytes of the first granule are not the
@@ -128,7 +171,7 @@ KX_LANE unsigned long long fp_splen_lane(const FPSpec& P, const unsigned long lo
 KX_LANE void fp_splice_lane(const FPSpec& P, const uint8_t* __restrict__ in, const unsigned long long* __restrict__ off, unsigned long long n,
                             const unsigned long long* __restrict__ d0, const uint8_t* __restrict__ pout,
                             const unsigned long long* __restrict__ poff, const unsigned long long* __restrict__ ooff,
-                            unsigned long long total, uint8_t* __restrict__ out, unsigned long long g) {
+                            unsigned long long total, uint8_t* __restrict__ out, unsigned long long g, const KVSpec* kv = nullptr) {
   enum { OUT = 0, OFS = 1, SEP = 2, SFX = 3 };
   const unsigned long long lead = (unsigned long long)((uintptr_t)out & 15);
   const unsigned long long p0 = (g << 4) < lead ? 0ull : (g << 4) - lead;
@@ -139,6 +182,8 @@ KX_LANE void fp_splice_lane(const FPSpec& P, const uint8_t* __restrict__ in, con
   unsigned long long e, be, da, m, a, c, j, ps, pe;
   uint32_t t, phase;
   const uint8_t* src;
+  const uint8_t* krow = nullptr;                                // keyed: the record's row of kdoc
+  bool has;                                                     // the record has an output (always, but in a keyed run)
   auto output = [&] {                                           // the piece at ps is output j of item t
     const unsigned long long b = poff[a + j];
     phase = OUT; pe = ps + (poff[a + j + 1] - b); src = pout + b;
@@ -146,16 +191,18 @@ KX_LANE void fp_splice_lane(const FPSpec& P, const uint8_t* __restrict__ in, con
   auto separator = [&] { phase = SEP; pe = ps + (P.keep ? e - be : 0ull); src = in + be; };
   auto item = [&] {                                             // from item t on, the first one with a field; false: none
     for (; t < P.n_items; ++t) {
-      fp_item(P, t, da, m, a, c);
+      fp_item(P, t, da, m, a, c, krow);
       if (c) return true;
     }
     return false;
   };
-  auto enter = [&] {                                            // record r: its first output (it has one)
+  auto enter = [&] {                                            // record r: its first output, if it has one
     e = off[r + 1]; be = fp_body_end(P, e, r); da = d0[r]; m = d0[r + 1] - da;
+    if (kv) krow = kv->kdoc + 16 * r;
     t = 0; j = 0; ps = 0;
-    (void)item();
+    has = item();
   };
+  auto first = [&] { if (has) output(); else separator(); };    // the piece at the record's first byte
   auto advance = [&] {
     ps = pe;
     if (phase == OUT) {                                         // OFS if an output follows, in this item or a later one
@@ -166,7 +213,7 @@ KX_LANE void fp_splice_lane(const FPSpec& P, const uint8_t* __restrict__ in, con
     else { phase = SFX; pe = ~0ull; }
   };
   enter();
-  if (p0 == rb) output();
+  if (p0 == rb || !has) first();
   else {
     const unsigned long long k0 = p0 - rb;
     for (;;) {                                                  // the item that holds byte k0, or the OFS in front of it
@@ -195,7 +242,7 @@ KX_LANE void fp_splice_lane(const FPSpec& P, const uint8_t* __restrict__ in, con
     if (pos >= re) {   // (pos < total = ooff[n]: r stays below n; a record with no output is stepped over)
       do { ++r; rb = re; re = ooff[r + 1]; } while (pos >= re);
       enter();
-      output();
+      first();
     }
     const unsigned long long k = pos - rb;
     while (k >= pe) advance();

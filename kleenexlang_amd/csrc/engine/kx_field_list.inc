@@ -204,7 +204,7 @@ __global__ __launch_bounds__(FLD_GT) void k_flsplice(const uint8_t* __restrict__
     auto ostart = [&](unsigned long long t) { return (fb[da + t] - s) - (coff[da + t] - coff[da]) + (poff[da + t] - poff[da]); };
     auto enter = [&] {                                          // record r from its first byte: gap 0
       s = off[r]; e = off[r + 1]; be = fld_body_end(e, r, F); da = d0[r]; m = d0[r + 1] - da;
-      j = 0; phase = GAP; ps = 0; pe = fb[da] - s; src = in + s;
+      j = 0; phase = GAP; ps = 0; pe = (m ? fb[da] : be) - s; src = in + s;   // (keyed runs: no document, gap 0 is the whole body)
     };
     auto advance = [&] {
       if (phase == GAP && j < m) {                              // gap j -> output j
@@ -260,10 +260,11 @@ __global__ __launch_bounds__(FLD_GT) void k_flsplice(const uint8_t* __restrict__
 // bytes for the ranges' table; with a projection (kx_field_project.inc) 256 for the items'.
 struct FieldListWs {
   BatchWs::Buf ctr, rng, itm, cnt, d0, nf, fb, fe, len, coff, comp, pout, poff, drec, wsum, woff, flags;
+  BatchWs::Buf ktab, dkey, kdoc;   // keyed runs (kx_field_keys.inc): the names' table, a byte per document, with a projection 16 per record
   hipEvent_t ev[12] = {};
   bool have_events = false;
   ~FieldListWs() {
-    for (BatchWs::Buf* b : {&ctr, &rng, &itm, &cnt, &d0, &nf, &fb, &fe, &len, &coff, &comp, &pout, &poff, &drec, &wsum, &woff, &flags}) if (b->p) (void)hipFree(b->p);
+    for (BatchWs::Buf* b : {&ctr, &rng, &itm, &cnt, &d0, &nf, &fb, &fe, &len, &coff, &comp, &pout, &poff, &drec, &wsum, &woff, &flags, &ktab, &dkey, &kdoc}) if (b->p) (void)hipFree(b->p);
     if (have_events) for (auto& e : ev) (void)hipEventDestroy(e);
   }
 };

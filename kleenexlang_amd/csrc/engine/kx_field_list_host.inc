@@ -40,11 +40,21 @@ int checkFieldList(const kx_batch_field_list& l, const char* who) {
 // items' table; without it every launch and every argument is what it is without the parameter.  With `identity`
 // (kx_run_batch_field_header; with `proj` only) step 4 is left out: the gathered fields — with a codec the decoded values — and
 // their offsets stand in for the program's outputs and theirs, and the document records are zeroed (every one accepted); steps 4v,
-// 5 and 6 run as they are.  Without it every launch and every argument is what it is without the parameter.
+// 5 and 6 run as they are.  Without it every launch and every argument is what it is without the parameter.  With `keyed`
+// (kx_run_batch_field_keys, kx_field_keys_host.inc, whose checks have passed; l->n_ranges is 0 and the ranges' table is not read)
+// steps 1 and 2 are k_kvcount and k_kvlocate (kx_field_keys.inc; `words` says how fields are cut), nf holds the masks of the names
+// found, a record without a document may be an accepted one, step 5 is k_kvsplen or with `proj` k_kpsplen, and with `proj` step 6
+// is k_kpsplice; a call without any document skips steps 2 to 4v as ever and still writes its accepted records.  Without it
+// every launch and every argument is what it is without the parameter.
+struct KeyedRun {
+  uint8_t tab[64 + 16 * 255];    // KVSpec::tab: 16 lengths, 16 offsets (16 bits each), the names' bytes
+  uint32_t all, req, kv;         // the masks of the listed and of the required names; the key separator
+};
+
 int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint64_t n_docs, const kx_batch_field_list* l,
                  const kx_field_codec* codec, void* d_out, size_t cap, uint64_t* d_out_off, kx_batch_doc* d_docs, uint32_t* d_fail_field,
                  size_t* out_len, kx_batch_stats* stats, void* stream, const char* who, bool words = false,
-                 const kx_field_project* proj = nullptr, bool identity = false) {
+                 const kx_field_project* proj = nullptr, bool identity = false, const KeyedRun* keyed = nullptr) {
   if (n_docs && (!d_in_off || !d_out_off || !d_docs)) return setErr(KX_E_ARG, std::string(who) + ": offsets, output offsets and document records are required");
   if (n_docs >= 0xFFFFFFFFull) return setErr(KX_E_ARG, std::string(who) + ": at most 2^32 - 2 documents per call");
   *out_len = 0;
@@ -72,6 +82,8 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
   int rc = BatchWs::ensure(W.ctr, FC_N * 8);
   if (!rc) rc = BatchWs::ensure(W.rng, 16 * 8);
   if (!rc && proj) rc = BatchWs::ensure(W.itm, 32 * 8);
+  if (!rc && keyed) rc = BatchWs::ensure(W.ktab, sizeof keyed->tab);
+  if (!rc && keyed && proj) rc = BatchWs::ensure(W.kdoc, nd * 16);
   if (!rc) rc = BatchWs::ensure(W.d0, (nd + 1) * 8);
   if (!rc) rc = BatchWs::ensure(W.nf, nd * 8);
   if (!rc) rc = BatchWs::ensure(W.cnt, nd * sizeof(BDoc));
@@ -112,12 +124,16 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
       }
       hitm[j] = rk;
       hitm[16 + j] = !in ? 0ull : proj->items[j].hi ? (unsigned long long)proj->items[j].hi - proj->items[j].lo + 1 : FL_OPEN;
+      if (keyed) { hitm[j] = in ? proj->items[j].hi : 0ull; hitm[16 + j] = in ? 1ull : 0ull; }   // (an item is a name: its index, one document)
     }
   }
+  KVSpec KV{};                   // keyed: the names' table; dkey and kdoc once they are allocated
+  if (keyed) KV = KVSpec{(const uint8_t*)W.ktab.p, nullptr, proj ? (const uint8_t*)W.kdoc.p : nullptr, keyed->all, keyed->req, keyed->kv};
   // the offsets, checked on the device before any kernel reads a record
   HIPCHECK(hipMemsetAsync(ctr, 0, FC_N * 8, sm));
   HIPCHECK(hipMemcpyAsync(W.rng.p, hrng, sizeof hrng, hipMemcpyHostToDevice, sm));   // (hrng lives until the sync below)
   if (proj) HIPCHECK(hipMemcpyAsync(W.itm.p, hitm, sizeof hitm, hipMemcpyHostToDevice, sm));   // (and hitm)
+  if (keyed) HIPCHECK(hipMemcpyAsync(W.ktab.p, keyed->tab, sizeof keyed->tab, hipMemcpyHostToDevice, sm));   // (the caller's: it outlives the call)
   hipLaunchKernelGGL(k_fcheck, dim3((uint32_t)((nd + 255) / 256)), dim3(256), 0, sm, off, (unsigned long long)nd, L.F, ctr);
   HIPCHECK(hipGetLastError());
   unsigned long long hc[FC_N] = {}, ends[2] = {0, 0};
@@ -147,6 +163,11 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
   if (timing) HIPCHECK(hipEventRecord(W.ev[0], sm));
   auto* const count = words ? (mode == FLD_ESCAPED ? &k_fwcount<FLD_ESCAPED> : mode == FLD_QUOTED ? &k_fwcount<FLD_QUOTED> : &k_fwcount<FLD_PLAIN>)
                             : (mode == FLD_ESCAPED ? &k_flcount<FLD_ESCAPED> : mode == FLD_QUOTED ? &k_flcount<FLD_QUOTED> : &k_flcount<FLD_PLAIN>);
+  if (keyed) {
+    auto* const kcount = words ? (mode == FLD_ESCAPED ? &k_kvcount<FLD_ESCAPED, true> : mode == FLD_QUOTED ? &k_kvcount<FLD_QUOTED, true> : &k_kvcount<FLD_PLAIN, true>)
+                               : (mode == FLD_ESCAPED ? &k_kvcount<FLD_ESCAPED, false> : mode == FLD_QUOTED ? &k_kvcount<FLD_QUOTED, false> : &k_kvcount<FLD_PLAIN, false>);
+    hipLaunchKernelGGL(kcount, dim3(bgrid), dim3(FLD_BT), 0, sm, in, off, (unsigned long long)nd, L.F, KV, cnt, nf);
+  } else
   hipLaunchKernelGGL(count, dim3(bgrid), dim3(FLD_BT), 0, sm, in, off, (unsigned long long)nd, L, cnt, nf);
   if (timing) HIPCHECK(hipEventRecord(W.ev[1], sm));
   scanLens(cnt, nd, d0);
@@ -167,6 +188,7 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
     for (BatchWs::Buf* b : {&W.coff, &W.poff}) if (!rc) rc = BatchWs::ensure(*b, (ndocs + 1) * 8);
     if (!rc) rc = BatchWs::ensure(W.len, ndocs * sizeof(BDoc));
     if (!rc) rc = BatchWs::ensure(W.drec, ndocs * sizeof(kx_batch_doc));
+    if (!rc && keyed) rc = BatchWs::ensure(W.dkey, ndocs);
     for (BatchWs::Buf* b : {&W.wsum, &W.woff}) if (!rc) rc = BatchWs::ensure(*b, (size_t)((ndocs + 1 + 1023) / 1024) * 8);
     if (rc) return rc;
     fb = (unsigned long long*)W.fb.p; fe = (unsigned long long*)W.fe.p; coff = (unsigned long long*)W.coff.p; poff = (unsigned long long*)W.poff.p;
@@ -182,6 +204,13 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
     if (timing) HIPCHECK(hipEventRecord(W.ev[3], sm));
     auto* const locate = words ? (mode == FLD_ESCAPED ? &k_fwlocate<FLD_ESCAPED> : mode == FLD_QUOTED ? &k_fwlocate<FLD_QUOTED> : &k_fwlocate<FLD_PLAIN>)
                                : (mode == FLD_ESCAPED ? &k_fllocate<FLD_ESCAPED> : mode == FLD_QUOTED ? &k_fllocate<FLD_QUOTED> : &k_fllocate<FLD_PLAIN>);
+    if (keyed) {
+      KV.dkey = (const uint8_t*)W.dkey.p;
+      auto* const klocate = words ? (mode == FLD_ESCAPED ? &k_kvlocate<FLD_ESCAPED, true> : mode == FLD_QUOTED ? &k_kvlocate<FLD_QUOTED, true> : &k_kvlocate<FLD_PLAIN, true>)
+                                  : (mode == FLD_ESCAPED ? &k_kvlocate<FLD_ESCAPED, false> : mode == FLD_QUOTED ? &k_kvlocate<FLD_QUOTED, false> : &k_kvlocate<FLD_PLAIN, false>);
+      hipLaunchKernelGGL(klocate, dim3(bgrid), dim3(FLD_BT), 0, sm, in, off, (unsigned long long)nd, L.F, KV, (const unsigned long long*)d0, fb, fe, len,
+                         (uint8_t*)W.dkey.p, proj ? (uint8_t*)W.kdoc.p : nullptr);
+    } else
     hipLaunchKernelGGL(locate, dim3(bgrid), dim3(FLD_BT), 0, sm, in, off, (unsigned long long)nd, L, (const unsigned long long*)d0, fb, fe, len);
     if (timing) HIPCHECK(hipEventRecord(W.ev[4], sm));
     scanLens(len, ndocs, coff);
@@ -267,7 +296,14 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
   // 5. the records' results and output lengths, and their scan into the caller's offsets
   BDoc* rlen = cnt;   // (the counts have been scanned into d0)
   if (timing) HIPCHECK(hipEventRecord(W.ev[8], sm));
-  if (proj)
+  if (keyed && proj)
+    hipLaunchKernelGGL(k_kpsplen, dim3(bgrid), dim3(FLD_BT), 0, sm, off, (unsigned long long)nd, P, KV, (const unsigned long long*)d0,
+                       (const unsigned long long*)nf, (const unsigned long long*)poff, (const kx_batch_doc*)drec, d_docs, d_fail_field, rlen, ctr);
+  else if (keyed)
+    hipLaunchKernelGGL(k_kvsplen, dim3(bgrid), dim3(FLD_BT), 0, sm, off, (unsigned long long)nd, L.F, KV, (const unsigned long long*)d0,
+                       (const unsigned long long*)nf, (const unsigned long long*)coff, (const unsigned long long*)poff, (const kx_batch_doc*)drec,
+                       d_docs, d_fail_field, (unsigned long long)l->suffix_len, rlen, ctr);
+  else if (proj)
     hipLaunchKernelGGL(k_fpsplen, dim3(bgrid), dim3(FLD_BT), 0, sm, off, (unsigned long long)nd, P, (const unsigned long long*)d0,
                        (const unsigned long long*)nf, (const unsigned long long*)poff, (const kx_batch_doc*)drec, d_docs, d_fail_field, rlen, ctr);
   else
@@ -290,7 +326,11 @@ int runFieldList(kx_program* p, const void* d_in, const uint64_t* d_in_off, uint
   if (total > cap || (total && !d_out)) return setErr(KX_E_CAPACITY, "output buffer too small");
   // 6. the splice
   if (timing) HIPCHECK(hipEventRecord(W.ev[10], sm));
-  if (total && proj)
+  if (total && proj && keyed)
+    hipLaunchKernelGGL(k_kpsplice, granGrid(total), dim3(FLD_GT), 0, sm, in, off, (unsigned long long)nd, P, KV, (const unsigned long long*)d0,
+                       spliced ? spliced : pbytes, (const unsigned long long*)poff, (const unsigned long long*)d_out_off, total,
+                       (uint8_t*)d_out);
+  else if (total && proj)
     hipLaunchKernelGGL(k_fpsplice, granGrid(total), dim3(FLD_GT), 0, sm, in, off, (unsigned long long)nd, P, (const unsigned long long*)d0,
                        spliced ? spliced : pbytes, (const unsigned long long*)poff, (const unsigned long long*)d_out_off, total,
                        (uint8_t*)d_out);

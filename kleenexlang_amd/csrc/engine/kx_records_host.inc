@@ -27,7 +27,9 @@
 // fields (kx_run_records_fd_field_list) it calls kx_run_batch_field_list the same way; the report lines name the field.  On unquoted
 // values (kx_run_records_fd_field_values) it calls kx_run_batch_field_values with the list and a codec whose one special byte is the
 // record separator.  On words (kx_run_records_fd_field_words) it calls kx_run_batch_field_words with the list, fs = 0 and, with
-// `unquote`, that codec; checkRecordsOpts has the blank rules.  Projected (kx_run_records_fd_field_project) RecordsRun holds the
+// `unquote`, that codec; checkRecordsOpts has the blank rules.  By key (kx_run_records_fd_field_keys) RecordsRun holds a
+// kx_field_keys with its own copy of the names, calls kx_run_batch_field_keys's driver and names the field of a report line by
+// its key.  Projected (kx_run_records_fd_field_project) RecordsRun holds the
 // kx_field_project beside the ranges, which are the normal form of its items' union, and calls kx_run_batch_field_project for the
 // carried record and the window's records alike, with the codec and the words flag as above.
 //
@@ -256,6 +258,8 @@ struct RecordsRun {
   kx_field_codec codec{};                              // ... on their values (size != 0: kx_run_batch_field_values; special = the separator)
   bool words = false;                                  // ... which are the body's words (kx_run_batch_field_words; fsep is not used)
   kx_field_project proj{};                             // ... projected (size != 0: kx_run_batch_field_project; ranges = the items' union)
+  kx_field_keys keys{};                                // field mode by key (size != 0: kx_run_batch_field_keys; n_ranges is 0, proj's items are names)
+  std::vector<std::string> key_names;                  //   ... whose names these are (keys.names point into them)
   uint64_t header = 0;                                 // the first `header` records are header records (kx_run_records_fd_table)
   kx_field_range titems[KX_FIELD_ITEMS] = {};          // ... and these items, some of them names (lo = 0, hi = the index into `names`),
   uint32_t n_titems = 0;                               //   become ranges (and proj.items) when record `header` is in hand
@@ -281,12 +285,16 @@ struct RecordsRun {
     for (auto& e : ev) if (e) (void)hipEventDestroy(e);
   }
 
-  // ff: with a list, the field number of every record's line
+  // ff: with a list, the field number of every record's line; by key, 1 + the index of the name the line names
   int report(const kx_batch_doc* d, uint64_t n, uint64_t first_rec, const uint32_t* ff = nullptr) {
     if (report_fd < 0) return 0;
     std::string s;
+    auto name = [&](uint64_t i) { return ff[i] >= 1 && ff[i] <= key_names.size() ? kxPrintableName(key_names[ff[i] - 1]) : std::string("?"); };
     for (uint64_t i = 0; i < n; ++i)
-      if (d[i].status == 2) s += "Record " + std::to_string(first_rec + i) + " has no field " + std::to_string(ff ? ff[i] : field) + "!\n";
+      if (d[i].status == 2 && keys.size) s += "Record " + std::to_string(first_rec + i) + " has no field " + name(i) + "!\n";
+      else if (d[i].status && keys.size)
+        s += "Match error at input symbol " + std::to_string(d[i].fail_pos) + " in field " + name(i) + " of record " + std::to_string(first_rec + i) + "!\n";
+      else if (d[i].status == 2) s += "Record " + std::to_string(first_rec + i) + " has no field " + std::to_string(ff ? ff[i] : field) + "!\n";
       else if (d[i].status && ff)
         s += "Match error at input symbol " + std::to_string(d[i].fail_pos) + " in field " + std::to_string(ff[i]) + " of record " +
              std::to_string(first_rec + i) + "!\n";
@@ -416,7 +424,12 @@ struct RecordsRun {
     ll.quote = fl.quote; ll.escape = fl.escape; ll.sep_len = fl.sep_len; ll.last_whole = fl.last_whole; ll.keep_sep = fl.keep_sep;
     ll.suffix_len = fl.suffix_len;
     memcpy(ll.suffix, fl.suffix, sizeof ll.suffix);
+    const bool listed = n_ranges || keys.size;       // the call fills ffield
     auto run = [&](void* d_out, size_t cap, size_t* ol, kx_batch_stats* bs) {
+      if (keys.size)
+        return fieldKeysEntry("kx_run_records_fd_field_keys", o.mode != KX_RECORDS_RS ? (int)o.sep : o.rs_len == 1 ? (int)o.rs[0] : -1, p, in, d_o, ndocs,
+                              &ll, &keys, codec.size ? &codec : nullptr, proj.size ? &proj : nullptr, d_out, cap, (uint64_t*)ooff.p,
+                              (kx_batch_doc*)docs.p, (uint32_t*)ffield.p, ol, bs, nullptr);
       if (identity)
         return kx_run_batch_field_header(p, in, d_o, ndocs, &ll, codec.size ? &codec : nullptr, &proj, d_out, cap, (uint64_t*)ooff.p,
                                          (kx_batch_doc*)docs.p, (uint32_t*)ffield.p, ol, bs, nullptr);
@@ -437,7 +450,7 @@ struct RecordsRun {
     };
     int rc = BatchWs::ensure(ooff, (ndocs + 1) * 8);
     if (!rc) rc = BatchWs::ensure(docs, ndocs * sizeof(kx_batch_doc));
-    if (!rc && n_ranges) rc = BatchWs::ensure(ffield, ndocs * 4);
+    if (!rc && listed) rc = BatchWs::ensure(ffield, ndocs * 4);
     if (rc) return rc;
     kx_batch_stats bs{};
     size_t ol = 0;
@@ -463,9 +476,9 @@ struct RecordsRun {
       st.records_rejected += bs.docs_rejected;
       std::vector<kx_batch_doc> h(ndocs);
       HIPCHECK(hipMemcpy(h.data(), docs.p, ndocs * sizeof(kx_batch_doc), hipMemcpyDeviceToHost));
-      std::vector<uint32_t> hf(n_ranges ? ndocs : 0);
-      if (n_ranges) HIPCHECK(hipMemcpy(hf.data(), ffield.p, ndocs * 4, hipMemcpyDeviceToHost));
-      return report(h.data(), ndocs, first_rec, n_ranges ? hf.data() : nullptr);
+      std::vector<uint32_t> hf(listed ? ndocs : 0);
+      if (listed) HIPCHECK(hipMemcpy(hf.data(), ffield.p, ndocs * 4, hipMemcpyDeviceToHost));
+      return report(h.data(), ndocs, first_rec, listed ? hf.data() : nullptr);
     }
     return 0;
   }
@@ -676,7 +689,8 @@ int checkRecordsOpts(const kx_records_opts& o, const char* who, int fs = -1, boo
 // the stream on in_fd in record mode as `o` says (checkRecordsOpts has passed)
 int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o, int report_fd, kx_records_stats* stats, uint32_t field = 0,
                  uint8_t fsep = 0, const kx_field_range* ranges = nullptr, uint32_t n_ranges = 0, bool values = false, bool words = false,
-                 const kx_field_project* proj = nullptr, const kx_records_table* t = nullptr, const char* who = "") {
+                 const kx_field_project* proj = nullptr, const kx_records_table* t = nullptr, const char* who = "",
+                 const kx_field_keys* keys = nullptr) {
   if (!p) return setErr(KX_E_ARG, "null argument");
   if (p->cfg.phase) return setErr(KX_E_ARG, "record mode runs every phase: kx_config::phase must be 0");
   const double t_begin = FdStream::nowMs();
@@ -693,6 +707,11 @@ int runRecordsFd(kx_program* p, int in_fd, int out_fd, const kx_records_opts& o,
   R.n_ranges = n_ranges; R.words = words;
   if (n_ranges) memcpy(R.ranges, ranges, n_ranges * sizeof(kx_field_range));
   if (proj) R.proj = *proj;
+  if (keys) {   // (the names are copied: the batch calls read them window after window)
+    R.keys = *keys;
+    for (uint32_t j = 0; j < keys->n_names; ++j) R.key_names.emplace_back((const char*)keys->names[j], keys->name_len[j]);
+    for (uint32_t j = 0; j < keys->n_names; ++j) R.keys.names[j] = (const uint8_t*)R.key_names[j].data();
+  }
   if (t) {   // header records, and items that may be names (checkTable has passed): without a name the caller has resolved them
     R.header = t->header; R.who = who;
     for (uint32_t j = 0; j < t->n_items; ++j) if (t->items[j].lo == 0) R.resolved = false;
@@ -820,6 +839,46 @@ extern "C" int kx_run_records_fd_field_project(kx_program* p, int in_fd, int out
   memcpy(pr.items, items, n_items * sizeof(kx_field_range));
   if (ofs_len) memcpy(pr.ofs, ofs, ofs_len);
   return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, 0, words ? (uint8_t)0 : fs, ranges, n_ranges, unquote, words, &pr);
+}
+
+extern "C" int kx_run_records_fd_field_keys(kx_program* p, int in_fd, int out_fd, const kx_records_opts* o, const kx_field_keys* keys, uint8_t fs,
+                                            const uint32_t* items, uint32_t n_items, const uint8_t* ofs, uint32_t ofs_len, int report_fd,
+                                            kx_records_stats* stats) {
+  static const char* const who = "kx_run_records_fd_field_keys";
+  auto no = [&](const char* what) { return setErr(KX_E_ARG, std::string(who) + ": " + what); };
+  if (!o || !keys) return setErr(KX_E_ARG, "null argument");
+  if (keys->size != sizeof(kx_field_keys)) return no("kx_field_keys::size is not this library's");
+  if (keys->flags & ~(KX_KEYS_WORDS | KX_KEYS_UNQUOTE | KX_KEYS_ONLY)) return no("unknown flag bits");
+  const bool words = (keys->flags & KX_KEYS_WORDS) != 0, unquote = (keys->flags & KX_KEYS_UNQUOTE) != 0, only = (keys->flags & KX_KEYS_ONLY) != 0;
+  if (only && (!items || (ofs_len && !ofs))) return setErr(KX_E_ARG, "null argument");
+  if (const int rc = words ? checkRecordsOpts(*o, who, -1, true) : checkRecordsOpts(*o, who, fs)) return rc;
+  if (unquote && o->mode != KX_RECORDS_QUOTED && o->mode != KX_RECORDS_ESCAPED) return no("values need a quote or an escape byte");
+  kx_field_keys k = *keys;
+  k.flags = words ? KX_KEYS_WORDS : 0u;
+  kx_batch_field_list fr{};   // the framing the batch calls will have, for the keys' own rules
+  fr.size = sizeof fr; fr.fs = words ? (uint8_t)0 : fs;
+  fr.quote = o->mode == KX_RECORDS_QUOTED || o->mode == KX_RECORDS_ESCAPED ? o->quote : -1;
+  fr.escape = o->mode == KX_RECORDS_ESCAPED ? o->escape : -1;
+  if (const int rc = checkFieldKeys(k, fr, o->mode != KX_RECORDS_RS ? (int)o->sep : o->rs_len == 1 ? (int)o->rs[0] : -1, who)) return rc;
+  kx_field_project pr{};
+  if (only) {
+    if (n_items < 1 || n_items > KX_FIELD_ITEMS) return no("the list as written has 1 to 16 items");
+    if (ofs_len > 8) return no("the output field separator is at most 8 bytes");
+    pr.size = sizeof pr; pr.n_items = n_items; pr.ofs_len = ofs_len; pr.flags = words ? KX_PROJECT_WORDS : 0u;
+    for (uint32_t j = 0; j < n_items; ++j) {
+      if (items[j] >= k.n_names) return no("an item is the index of a name");
+      pr.items[j] = kx_field_range{0u, items[j]};
+    }
+    if (ofs_len) memcpy(pr.ofs, ofs, ofs_len);
+    if (unquote) {
+      if (ofs_len != 1) return no("on values the output field separator is exactly one byte");
+      if (ofs[0] == o->sep) return no("the output field separator cannot be the record separator");
+      if ((int)ofs[0] == o->quote) return no("the output field separator cannot be the quote byte");
+      if (o->mode == KX_RECORDS_ESCAPED && (int)ofs[0] == o->escape) return no("the output field separator cannot be the escape byte");
+      if (words && ofs[0] == 0x09) return no("on the values of words the output field separator cannot be the tab");
+    }
+  }
+  return runRecordsFd(p, in_fd, out_fd, *o, report_fd, stats, 0, words ? (uint8_t)0 : fs, nullptr, 0, unquote, words, only ? &pr : nullptr, nullptr, who, &k);
 }
 
 namespace {

@@ -32,7 +32,11 @@
 // --field, --fs, --unquote, --blanks, --only and --ofs refuse exits with status 2.  With `--header[=N]` (with --records; default 1)
 // the first N records are header records — never run, copied, or with --only projected like the records behind them — and the
 // items of --field may be NAMES of cells of header record N (kx_run_records_fd_table; the list's parser is kx_field_names.h): the
-// option's text is then parsed behind the option loop.  A name no cell has ends the run with status 2.
+// option's text is then parsed behind the option loop.  A name no cell has ends the run with status 2.  With `--keys[=C]` (with
+// --field, not with --header; default C: =) the fields are key=value pairs: every item of --field is a NAME (kx_field_keys.h; a
+// last `?` makes it optional), a name selects the first field whose bytes before its first live C spell it, and the program runs
+// on what follows that C (kx_run_records_fd_field_keys); a record that lacks a required name is reported as "Record R has no field
+// NAME!".  The option's text is parsed behind the option loop as well.
 //
 // BIN = this executable ++ KXP blob ++ libdir ++ trailer (see kexc main.cpp).
 // The engine is loaded with dlopen so that this file carries no HIP dependency.
@@ -51,6 +55,7 @@
 #include "../../../include/kxhip.h"
 #include "kx_field_list.h"
 #include "kx_field_names.h"
+#include "kx_field_keys.h"
 
 // The engine's switches are fields of kx_config (include/kxhip.h); the library reads no environment variable for them.  A produced
 // binary keeps honouring the variable names that earlier rounds' scripts use: they are read HERE, once, and mapped onto the struct.
@@ -102,7 +107,7 @@ static void usage(const char* name) {
   fprintf(stdout, "- \"%s --records ... --quote|--escape --field=K|LIST [--fs=F] --unquote\": the program runs on the unquoted value of every selected field; its output is quoted again as it needs.\n", name);
   fprintf(stdout, "- \"%s --records ... --field=K|LIST --blanks [--unquote]\": the fields are the words between runs of spaces and tabs (awk's default); every blank is copied as it is.\n", name);
   fprintf(stdout, "- \"%s --records ... --field=K|LIST [--fs=F | --blanks] [--unquote] --only [--ofs=STR]\": writes only the selected fields' outputs, in the order LIST is written (4,2 or 2,1,2), joined by STR (0 to 8 bytes; default F, or a space with --blanks).\n", name);
-  fprintf(stdout, "- \"%s --records ... --header[=N] [--field=LIST ...]\": the first N records (default 1) are header rows: never run, copied (with --only: projected), and LIST may name columns of row N (id,city or 2,name,5-; \\, is a comma in a name).\n", name);
+  fprintf(stdout, "- \"%s --records ... --header[=N] [--field=LIST ...]\": the first N records (default 1) are header rows: never run, copied (with --only: projected), and LIST may name columns of row N (id,city or 2,name,5-; \\, is a comma in a name). With --keys[=C] in place of --header the fields are key=value pairs (C, default =, ends the key) and LIST names keys (ts,msg? - a last ? makes one optional): the program runs on the value of the first field with each key.\n", name);
 }
 
 // --records=SEP, --quote=Q, --escape=E: one literal byte, or \n \t \r \0 \\ \xHH.  false if it is none of these.
@@ -190,7 +195,8 @@ int main(int argc, char** argv) {
                                          {"field", required_argument, 0, 'f'}, {"fs", required_argument, 0, 'F'},
                                          {"unquote", no_argument, 0, 'u'}, {"blanks", no_argument, 0, 'b'},
                                          {"only", no_argument, 0, 'y'}, {"ofs", required_argument, 0, 'O'},
-                                         {"header", optional_argument, 0, 'H'}, {0, 0, 0, 0}};
+                                         {"header", optional_argument, 0, 'H'}, {"keys", optional_argument, 0, 'K'},
+                                         {0, 0, 0, 0}};
   bool timing = false, records = false, quoted = false, escaped = false, sep_given = false, multi = false, chomp = false, ors_given = false;
   uint8_t sep = '\n', quote = '"', escape = '\\', rs[8] = {}, ors[8] = {};
   uint32_t rs_len = 0, ors_len = 0, field = 0;
@@ -207,8 +213,13 @@ int main(int argc, char** argv) {
   bool header_given = false, has_names = false;
   uint32_t header = 1;
   std::vector<KxFieldNameItem> named;            // --header with a name in --field: the list as written
-  for (int i = 1; i < argc && strcmp(argv[i], "--") != 0; ++i)   // (with --header the text of --field is parsed behind the loop)
+  bool keys_given = false;
+  uint8_t kvsep = '=';
+  KxFieldKeys keyed;                             // --keys: --field's names
+  for (int i = 1; i < argc && strcmp(argv[i], "--") != 0; ++i) {   // (with --header or --keys the text of --field is parsed behind the loop)
     if (!strcmp(argv[i], "--header") || !strncmp(argv[i], "--header=", 9)) header_given = true;
+    if (!strcmp(argv[i], "--keys") || !strncmp(argv[i], "--keys=", 7)) keys_given = true;
+  }
   // --field's text without names: null, or the exit status after the message
   auto parseFieldNumbers = [&](const char* text) -> int {
     n_ranges = 0; field = 0;
@@ -264,7 +275,11 @@ int main(int argc, char** argv) {
       case 'f':
         field_given = true;
         field_text = optarg;
-        if (!header_given) if (const int bad = parseFieldNumbers(optarg)) return bad;
+        if (!header_given && !keys_given) if (const int bad = parseFieldNumbers(optarg)) return bad;
+        break;
+      case 'K':
+        keys_given = true;
+        if (optarg && !parseSeparator(optarg, &kvsep)) { fprintf(stderr, "Invalid --keys: %s (one byte)\n", optarg); return 2; }
         break;
       case 'H': {
         header_given = true;
@@ -292,6 +307,14 @@ int main(int argc, char** argv) {
   }
   // (refused before the engine library is loaded)
   if (header_given && !records) { fprintf(stderr, "%s: --header needs --records\n", argv[0]); return 2; }
+  if (keys_given && !field_given) { fprintf(stderr, "%s: --keys needs --field\n", argv[0]); return 2; }
+  if (keys_given && header_given) { fprintf(stderr, "%s: --keys cannot be combined with --header\n", argv[0]); return 2; }
+  if (keys_given) {                    // --field's text: every item is a name
+    if (const char* why = kxParseFieldKeys(field_text, &keyed)) {
+      fprintf(stderr, "Invalid --field: %s (with --keys a list of at most 16 names such as ts,msg?: %s)\n", field_text, why);
+      return 2;
+    }
+  }
   if (header_given && field_given) {   // --field's text, which may hold names of header cells
     has_names = kxFieldTextHasName(field_text);
     if (!has_names) { if (const int bad = parseFieldNumbers(field_text)) return bad; }
@@ -327,8 +350,20 @@ int main(int argc, char** argv) {
   if (unquote && !quoted && !escaped) { fprintf(stderr, "%s: --unquote needs --quote or --escape\n", argv[0]); return 2; }
   if (only && !field_given) { fprintf(stderr, "%s: --only needs --field\n", argv[0]); return 2; }
   if (ofs_given && !only) { fprintf(stderr, "%s: --ofs needs --only\n", argv[0]); return 2; }
+  if (keys_given) {   // the key separator and the names beside the bytes of the framing
+    const int rsep = multi ? (rs_len == 1 ? (int)rs[0] : -1) : (int)sep;
+    if (const char* clash = kxFieldKeyByteClash(kvsep, blanks ? -1 : (int)fsep, blanks, rsep, quoted ? (int)quote : -1, escaped ? (int)escape : -1)) {
+      fprintf(stderr, "%s: the --keys character cannot be %s\n", argv[0], clash);
+      return 2;
+    }
+    for (const std::string& nm : keyed.names)
+      if (const char* clash = kxFieldKeyNameClash((const uint8_t*)nm.data(), nm.size(), kvsep, blanks ? -1 : (int)fsep, blanks, rsep)) {
+        fprintf(stderr, "%s: with --keys the name \"%s\" of --field cannot hold %s\n", argv[0], kxPrintableName(nm).c_str(), clash);
+        return 2;
+      }
+  }
   if (only) {   // the list as written (a plain number is the list K-K); its union is what the list's own parse gave
-    if (!has_names)
+    if (!has_names && !keys_given)
       if (const char* why = kxParseFieldOrder(field_text, items, &n_items, ranges, &n_ranges)) {
         fprintf(stderr, "Invalid --field: %s (with --only a list of at most 16 items such as 4,2 or 2,1,2: %s)\n", field_text, why);
         return 2;
@@ -340,7 +375,7 @@ int main(int argc, char** argv) {
     if (unquote && (multi ? rs_len == 1 && ofs[0] == rs[0] : ofs[0] == sep)) { fprintf(stderr, "%s: with --unquote --ofs cannot be the record separator\n", argv[0]); return 2; }
     if (unquote && blanks && ofs[0] == '\t') { fprintf(stderr, "%s: with --unquote and --blanks --ofs cannot be the tab\n", argv[0]); return 2; }
   }
-  if ((unquote || blanks) && !n_ranges && !has_names) { ranges[0] = kx_field_range{field, field}; n_ranges = 1; }   // --field=K on values or words: the list K-K
+  if ((unquote || blanks) && !n_ranges && !has_names && !keys_given) { ranges[0] = kx_field_range{field, field}; n_ranges = 1; }   // --field=K on values or words: the list K-K
   struct timeval t0, t1;
   if (timing) gettimeofday(&t0, nullptr);
 
@@ -367,17 +402,19 @@ int main(int argc, char** argv) {
     decltype(&kx_run_records_fd_field_words) runw = nullptr;
     decltype(&kx_run_records_fd_field_project) runp = nullptr;
     decltype(&kx_run_records_fd_table) runt = nullptr;
+    decltype(&kx_run_records_fd_field_keys) runk = nullptr;
     if (!runr) return 1;
+    if (keys_given && !(runk = (decltype(runk))engineSymbol(h, argv[0], "kx_run_records_fd_field_keys", "--keys needs"))) return 1;
     if (header_given && !(runt = (decltype(runt))engineSymbol(h, argv[0], "kx_run_records_fd_table", "--header needs"))) return 1;
-    if (!runt && quoted && !(runq = (decltype(runq))engineSymbol(h, argv[0], "kx_run_records_fd_quoted", "--quote needs"))) return 1;
-    if (!runt && escaped && !(rune = (decltype(rune))engineSymbol(h, argv[0], "kx_run_records_fd_escaped", "--escape needs"))) return 1;
-    if (!runt && multi && !(runm = (decltype(runm))engineSymbol(h, argv[0], "kx_run_records_fd_rs", "--rs needs"))) return 1;
-    if (!runt && only && !(runp = (decltype(runp))engineSymbol(h, argv[0], "kx_run_records_fd_field_project", "--only needs"))) return 1;
-    if (!runt && field_given && !n_ranges && !(runf = (decltype(runf))engineSymbol(h, argv[0], "kx_run_records_fd_fields", "--field needs"))) return 1;
-    if (!runt && blanks && !only && !(runw = (decltype(runw))engineSymbol(h, argv[0], "kx_run_records_fd_field_words", "--blanks needs"))) return 1;
-    if (!runt && n_ranges && !unquote && !blanks && !only && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_list", "--field=LIST needs"))) return 1;
-    if (!runt && unquote && !blanks && !only && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_values", "--unquote needs"))) return 1;   // (the same signature)
-    if (!runt && framing && !(runo = (decltype(runo))engineSymbol(h, argv[0], "kx_run_records_fd_opts", "--chomp and --ors need"))) return 1;
+    if (!runt && !runk && quoted && !(runq = (decltype(runq))engineSymbol(h, argv[0], "kx_run_records_fd_quoted", "--quote needs"))) return 1;
+    if (!runt && !runk && escaped && !(rune = (decltype(rune))engineSymbol(h, argv[0], "kx_run_records_fd_escaped", "--escape needs"))) return 1;
+    if (!runt && !runk && multi && !(runm = (decltype(runm))engineSymbol(h, argv[0], "kx_run_records_fd_rs", "--rs needs"))) return 1;
+    if (!runt && !runk && only && !(runp = (decltype(runp))engineSymbol(h, argv[0], "kx_run_records_fd_field_project", "--only needs"))) return 1;
+    if (!runt && !runk && field_given && !n_ranges && !(runf = (decltype(runf))engineSymbol(h, argv[0], "kx_run_records_fd_fields", "--field needs"))) return 1;
+    if (!runt && !runk && blanks && !only && !(runw = (decltype(runw))engineSymbol(h, argv[0], "kx_run_records_fd_field_words", "--blanks needs"))) return 1;
+    if (!runt && !runk && n_ranges && !unquote && !blanks && !only && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_list", "--field=LIST needs"))) return 1;
+    if (!runt && !runk && unquote && !blanks && !only && !(runl = (decltype(runl))engineSymbol(h, argv[0], "kx_run_records_fd_field_values", "--unquote needs"))) return 1;   // (the same signature)
+    if (!runt && !runk && framing && !(runo = (decltype(runo))engineSymbol(h, argv[0], "kx_run_records_fd_opts", "--chomp and --ors need"))) return 1;
     // record mode is where the single-document route is unusable (a third of a millisecond per record): stages with register
     // actions are replayed by the batch kernels unless KX_BATCH_ACTIONS=0 asks for the route
     if (!cfg.batch_actions) cfg.batch_actions = 2;
@@ -426,7 +463,16 @@ int main(int argc, char** argv) {
       memcpy(o.rs, rs, 8); o.rs_len = rs_len;
       o.chomp = chomp ? 1u : 0u;
       memcpy(o.ors, ors, 8); o.ors_len = ors_len;
-      rc = only        ? runp(prog, STDIN_FILENO, STDOUT_FILENO, &o, items, n_items, fsep, ofs, ofs_len,
+      kx_field_keys kk{};
+      uint32_t kitems[KX_FIELD_ITEMS] = {};
+      if (keys_given) {
+        kk.size = sizeof kk; kk.n_names = (uint32_t)keyed.names.size(); kk.optional_mask = keyed.optional_mask; kk.kv = kvsep;
+        kk.flags = (blanks ? KX_KEYS_WORDS : 0u) | (unquote ? KX_KEYS_UNQUOTE : 0u) | (only ? KX_KEYS_ONLY : 0u);
+        for (uint32_t j = 0; j < kk.n_names; ++j) { kk.names[j] = (const uint8_t*)keyed.names[j].data(); kk.name_len[j] = (uint32_t)keyed.names[j].size(); }
+        for (size_t j = 0; j < keyed.items.size(); ++j) kitems[j] = keyed.items[j];
+      }
+      rc = keys_given  ? runk(prog, STDIN_FILENO, STDOUT_FILENO, &o, &kk, fsep, kitems, (uint32_t)keyed.items.size(), ofs, ofs_len, STDERR_FILENO, &rs_stats)
+           : only      ? runp(prog, STDIN_FILENO, STDOUT_FILENO, &o, items, n_items, fsep, ofs, ofs_len,
                                 (blanks ? KX_PROJECT_WORDS : 0u) | (unquote ? KX_PROJECT_UNQUOTE : 0u), STDERR_FILENO, &rs_stats)
            : blanks    ? runw(prog, STDIN_FILENO, STDOUT_FILENO, &o, ranges, n_ranges, unquote ? 1 : 0, STDERR_FILENO, &rs_stats)
            : n_ranges  ? runl(prog, STDIN_FILENO, STDOUT_FILENO, &o, ranges, n_ranges, fsep, STDERR_FILENO, &rs_stats)

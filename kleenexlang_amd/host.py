@@ -40,15 +40,16 @@ class MatchError(KleenexError):
         super().__init__("Match error at input symbol %d!" % pos)
         self.pos = pos
         self.stage = stage
-        self.field = field      # field mode with a list: the number of the rejected field, `pos` counted inside it
+        self.field = field      # field mode with a list: the number of the rejected field, `pos` counted inside it (keys=: its name)
 
 
 class NoFieldError(KleenexError):
     """Field mode: the record has fewer fields than the one asked for.  `fields` = the fields it has."""
 
-    def __init__(self, fields):
-        super().__init__("the record has only %d field(s)" % fields)
+    def __init__(self, fields, field=None):
+        super().__init__("the record has only %d field(s)" % fields if field is None else "the record has no field %r" % (field,))
         self.fields = fields
+        self.field = field      # keys=: the first required name the record lacks (`fields` is then the mask of the names it has)
 
 
 class HeaderError(KleenexError):
@@ -808,6 +809,188 @@ def project_records_model(data, offsets, sep_len, last_whole, items, fs, quote=N
     return res
 
 
+def parse_field_keys(text):
+    """The LIST of `--field=LIST --keys` → (names, optional_mask, items): the DISTINCT names as bytes in the order of their first
+    item, bit t of the mask set if every item that names names[t] is optional, and the items as written as indices into names.
+    The text is cut at the commas that no backslash takes with it.  Every item is a name, an all-digits item too: its bytes (the
+    text's UTF-8) spelled as themselves or as \\n \\t \\r \\0 \\\\ \\, \\xHH, 1 to 255 of them; a last `?` that no backslash takes with it
+    is no byte of the name and makes the item optional (a literal last `?` is spelled \\x3F).  Raises ValueError for what the
+    command line refuses: a bad spelling, an empty name, one of more than 255 bytes, more than 16 items."""
+    if not isinstance(text, str):
+        raise TypeError("field list: a str such as 'ts,msg?', not %s" % type(text).__name__)
+    raw, cuts, taken, i = text.encode("utf-8", "surrogateescape"), [], set(), 0
+    while i < len(raw):
+        if raw[i] == 0x5C and i + 1 < len(raw):
+            i += 1
+            taken.add(i)
+        elif raw[i] == 0x2C:
+            cuts.append(i)
+        i += 1
+    names, items, required = [], [], 0
+    for b, e in zip([0] + [c + 1 for c in cuts], cuts + [len(raw)]):
+        optional = e > b and raw[e - 1] == 0x3F and (e - 1) not in taken
+        item, name, k = raw[b:e - 1 if optional else e], bytearray(), 0
+        while k < len(item):
+            if item[k] != 0x5C:
+                name.append(item[k])
+                k += 1
+                continue
+            c = item[k + 1:k + 2]
+            if c in (b"n", b"t", b"r", b"0", b"\\", b","):
+                name += {b"n": b"\n", b"t": b"\t", b"r": b"\r", b"0": b"\0", b"\\": b"\\", b",": b","}[c]
+                k += 2
+            elif c == b"x" and re.fullmatch(rb"[0-9a-fA-F]{2}", item[k + 2:k + 4]):
+                name.append(int(item[k + 2:k + 4], 16))
+                k += 4
+            else:
+                raise ValueError("field list %r: a backslash in a name starts \\n \\t \\r \\0 \\\\ \\, or \\xHH" % text)
+        if not name:
+            raise ValueError("field list %r: an empty name" % text)
+        if len(name) > FIELD_NAME_MAX:
+            raise ValueError("field list %r: a name has at most %d bytes" % (text, FIELD_NAME_MAX))
+        if len(items) == FIELD_ITEMS_MAX:
+            raise ValueError("field list %r: more than %d items" % (text, FIELD_ITEMS_MAX))
+        name = bytes(name)
+        if name not in names:
+            names.append(name)
+        items.append(names.index(name))
+        if not optional:
+            required |= 1 << items[-1]
+    return tuple(names), ((1 << len(names)) - 1) & ~required, tuple(items)
+
+
+def _check_field_keys(what, fields, optional, kv, fs, blanks, quote=None, escape=None, sep=None):
+    """The names of a keyed call: `fields`, 1 to 16 bytes names of 1 to 255 bytes (repeats allowed); `optional`, those of them a
+    record may lack; `kv`, the key separator C, which is not `fs` (with `blanks`: no blank), the quote, the escape or the one-byte
+    record separator `sep`; no name holds C, `fs` (a blank) or `sep` → (the distinct names, optional_mask, the items as indices,
+    C as an int)."""
+    if not isinstance(fields, (tuple, list)) or not fields or not all(isinstance(n, (bytes, bytearray)) for n in fields):
+        raise TypeError("%s: with keys= fields is a sequence of bytes names" % what)
+    if len(fields) > FIELD_ITEMS_MAX:
+        raise ValueError("%s: fields: %d items, at most %d" % (what, len(fields), FIELD_ITEMS_MAX))
+    c = _one_byte(kv, "key separator")
+    f = None if blanks else _one_byte(fs, "field separator")
+    s = None if sep is None else _one_byte(sep, "record separator")
+    if c == f or (blanks and c in BLANKS) or c == s:
+        raise ValueError("%s: keys: %r is also the field or the record separator" % (what, bytes([c])))
+    if (quote is not None and c == _one_byte(quote, "quote character")) or (escape is not None and c == _one_byte(escape, "escape character")):
+        raise ValueError("%s: keys: %r is also the quote or the escape character" % (what, bytes([c])))
+    names = []
+    for n in fields:
+        n = bytes(n)
+        if not 1 <= len(n) <= FIELD_NAME_MAX:
+            raise ValueError("%s: fields: a name has 1 to %d bytes, not %d" % (what, FIELD_NAME_MAX, len(n)))
+        if c in n or (f is not None and f in n) or (blanks and any(b in BLANKS for b in n)) or (s is not None and s in n):
+            raise ValueError("%s: fields: the name %r holds the key, the field or the record separator" % (what, n))
+        if n not in names:
+            names.append(n)
+    mask = 0
+    for n in optional:
+        if not isinstance(n, (bytes, bytearray)) or bytes(n) not in names:
+            raise ValueError("%s: optional: %r is no name of fields" % (what, n))
+        mask |= 1 << names.index(bytes(n))
+    return tuple(names), mask, tuple(names.index(bytes(n)) for n in fields), c
+
+
+def keyed_records_model(data, offsets, sep_len, last_whole, names, kv=b"=", fs=b"\t", quote=None, escape=None, blanks=False, optional=()):
+    """kx_run_batch_field_keys's view of its records in pure Python — the normative model of `--field=LIST --keys[=C]`.  The
+    records, their bodies and their fields are field_list_records_model's — with `blanks` (and fs None) the words of
+    blank_field_list_records_model.  Inside a field the KEY is the bytes before the field's first live `kv` byte — live under the
+    rule that makes an `fs` byte live: parity 0 and not escaped, with the record's running state — and the VALUE everything behind
+    that byte up to the field's end; a field without a live `kv` byte has no key, an empty key matches nothing, and keys are
+    compared as raw bytes.  Each of `names` (distinct bytes) selects the FIRST field that has it for a key.  A record that lacks a
+    name not in `optional` gives an int, the mask of the names it has (bit t: names[t]).  Any other record gives (gaps, fields,
+    separator): `fields` the m selected (t, value bytes) pairs in ADDRESS order and `gaps` the m + 1 byte strings around them — keys
+    and `kv` bytes included — so that the body is gaps[0] + fields[0][1] + gaps[1] + … + gaps[m]; m may be 0."""
+    if not isinstance(data, (bytes, bytearray, memoryview)):
+        raise TypeError("keyed_records_model: data must be bytes, not %s" % type(data).__name__)
+    if not isinstance(blanks, bool) or not isinstance(last_whole, bool):
+        raise TypeError("keyed_records_model: blanks and last_whole must be True or False")
+    if blanks and fs is not None:
+        raise ValueError("keyed_records_model: blanks= cannot be combined with an fs")
+    sep_len = _check_sep_len(sep_len)
+    given = list(names)
+    names, opt, _, c = _check_field_keys("keyed_records_model", given, optional, kv, fs, blanks, quote, escape)
+    if len(names) != len(given):
+        raise ValueError("keyed_records_model: the names are distinct")
+    f = None if blanks else _check_fs(fs, quote, escape)
+    if blanks:
+        _check_not_blank(quote, escape)
+    q = None if quote is None else _one_byte(quote, "quote character")
+    e = None if escape is None else _one_byte(escape, "escape character")
+    if q is not None and q == e:
+        raise ValueError("escape character: %r is also the quote character" % bytes([e]))
+    required = ((1 << len(names)) - 1) & ~opt
+    data, offs = bytes(data), [int(o) for o in offsets]
+    check_batch_offsets(offs, len(data))
+    n, res = len(offs) - 1, []
+    for i in range(n):
+        t = 0 if last_whole and i == n - 1 else sep_len
+        if offs[i + 1] - offs[i] < t:
+            raise ValueError("keyed_records_model: record %d is shorter than its separator (%d)" % (i, t))
+        body, sep = data[offs[i]:offs[i + 1] - t], data[offs[i + 1] - t:offs[i + 1]]
+        fields, firstc, begin, parity, esc = [], None, None if blanks else 0, 0, False   # fields: (begin, first live C or None, end)
+        for k, b in enumerate(body):
+            live = livec = False
+            if esc:
+                esc = False
+            elif e is not None and b == e:
+                esc = True
+            elif q is not None and b == q:
+                parity ^= 1
+            elif parity == 0:
+                live = b in BLANKS if blanks else b == f
+                livec = not live and b == c
+            if blanks:
+                if not live and begin is None:
+                    begin, firstc = k, None
+                elif live and begin is not None:
+                    fields.append((begin, firstc, k))
+                    begin = None
+            elif live:
+                fields.append((begin, firstc, k))
+                begin, firstc = k + 1, None
+            if livec and firstc is None:
+                firstc = k
+        if begin is not None:
+            fields.append((begin, firstc, len(body)))
+        found, sel = 0, []
+        for fbeg, fc, fend in fields:
+            key = body[fbeg:fc] if fc is not None else b""
+            if key in names and not found >> names.index(key) & 1:
+                found |= 1 << names.index(key)
+                sel.append((names.index(key), fc + 1, fend))
+        if required & ~found:
+            res.append(found)
+            continue
+        gaps, out, at = [], [], 0
+        for tix, vb, ve in sel:
+            gaps.append(body[at:vb])
+            out.append((tix, body[vb:ve]))
+            at = ve
+        gaps.append(body[at:])
+        res.append((gaps, out, sep))
+    return res
+
+
+class KxFieldKeys(ctypes.Structure):
+    """include/kxhip.h::kx_field_keys."""
+    _fields_ = [("size", ctypes.c_uint32), ("n_names", ctypes.c_uint32), ("names", ctypes.c_char_p * 16), ("name_len", ctypes.c_uint32 * 16),
+                ("optional_mask", ctypes.c_uint32), ("kv", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 4)]
+
+
+KX_KEYS_WORDS, KX_KEYS_UNQUOTE, KX_KEYS_ONLY = 1, 2, 4
+
+
+def field_keys_struct(names, optional_mask, kv, flags=0):
+    """A kx_field_keys for the distinct bytes `names`.  Nothing is checked here: the library does that."""
+    k = KxFieldKeys(size=ctypes.sizeof(KxFieldKeys), n_names=len(names), optional_mask=optional_mask, kv=kv, flags=flags)
+    for j, name in enumerate(names[:16]):
+        k.names[j], k.name_len[j] = bytes(name), len(name)
+    return k
+
+
 class KxFieldProject(ctypes.Structure):
     """include/kxhip.h::kx_field_project."""
     _fields_ = [("size", ctypes.c_uint32), ("n_items", ctypes.c_uint32), ("items", KxFieldRange * 16), ("ofs_len", ctypes.c_uint32),
@@ -1290,6 +1473,12 @@ def load_engine():
                                                         u32, ctypes.c_uint8, ctypes.c_char_p, u32, u32, ctypes.c_int,
                                                         ctypes.POINTER(KxRecordsStats)]
         lib.kx_run_batch_field_header.argtypes = lib.kx_run_batch_field_project.argtypes
+        lib.kx_run_batch_field_keys.argtypes = [vp, vp, vp, u64, ctypes.POINTER(KxBatchFieldList), ctypes.POINTER(KxFieldKeys),
+                                                ctypes.POINTER(KxFieldCodec), ctypes.POINTER(KxFieldProject), vp, sz, vp, vp, vp,
+                                                ctypes.POINTER(sz), ctypes.POINTER(KxBatchStats), vp]
+        lib.kx_run_records_fd_field_keys.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.POINTER(KxFieldKeys),
+                                                     ctypes.c_uint8, ctypes.POINTER(u32), u32, ctypes.c_char_p, u32, ctypes.c_int,
+                                                     ctypes.POINTER(KxRecordsStats)]
         lib.kx_run_records_fd_table.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), ctypes.POINTER(KxRecordsTable),
                                                 ctypes.c_int, ctypes.POINTER(KxRecordsStats)]
         lib.kx_run_records_fd_fields.argtypes = [vp, ctypes.c_int, ctypes.c_int, ctypes.POINTER(KxRecordsOpts), u32, ctypes.c_uint8,
@@ -1767,13 +1956,13 @@ class Program:
             frame.suffix[:len(suffix)] = bytes(suffix)
         return self._run_batch_call("run_batch_tensor", values, offsets, out, frame, None)
 
-    def _run_batch_call(self, what, values, offsets, out, frame, fields, codec=None, words=False, proj=None, identity=False):
+    def _run_batch_call(self, what, values, offsets, out, frame, fields, codec=None, words=False, proj=None, identity=False, keys=None):
         """The device part of run_batch_tensor (`frame`: a KxBatchFrame or None), run_batch_fields_tensor (`fields`: a
         KxBatchFields), run_batch_field_list_tensor (`fields`: a KxBatchFieldList, which adds the fail_field tensor to the
         result), run_batch_field_values_tensor (the same with `codec`: a KxFieldCodec) and run_batch_field_words_tensor (`words`;
         `codec` a KxFieldCodec or None) and run_batch_field_project_tensor (`proj`: a KxFieldProject, whose flags say whether the
-        fields are words; with `identity` kx_run_batch_field_header): the checks that need the tensors' device, the buffers, the size
-        query and the call."""
+        fields are words; with `identity` kx_run_batch_field_header) and run_batch_field_keys_tensor (`keys`: a KxFieldKeys; `codec`
+        and `proj` or None): the checks that need the tensors' device, the buffers, the size query and the call."""
         import torch
         if not values.is_cuda:
             raise EngineError("%s: values must be on a HIP device (there is no CPU fallback)" % what)
@@ -1798,7 +1987,14 @@ class Program:
             st = KxBatchStats()
             bptr = ctypes.c_void_p(buf.data_ptr() if buf is not None and buf.numel() else None)
             bcap = buf.numel() if buf is not None else 0
-            if proj is not None:
+            if keys is not None:
+                rc = self._lib.kx_run_batch_field_keys(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
+                                                       ctypes.byref(fields), ctypes.byref(keys), ctypes.byref(codec) if codec is not None else None,
+                                                       ctypes.byref(proj) if proj is not None else None, bptr, bcap,
+                                                       ctypes.c_void_p(out_off.data_ptr()), ctypes.c_void_p(docs.data_ptr()),
+                                                       ctypes.c_void_p(ffield.data_ptr()), ctypes.byref(ol), ctypes.byref(st),
+                                                       ctypes.c_void_p(stream))
+            elif proj is not None:
                 entry = self._lib.kx_run_batch_field_header if identity else self._lib.kx_run_batch_field_project
                 rc = entry(self._h, ctypes.c_void_p(vptr), ctypes.c_void_p(offsets.data_ptr()), n,
                            ctypes.byref(fields), ctypes.byref(codec) if codec is not None else None, ctypes.byref(proj), bptr, bcap,
@@ -2033,6 +2229,68 @@ class Program:
         proj.ofs[:len(ofs)] = ofs
         return self._run_batch_call(what, values, offsets, out, None, spec, codec, proj=proj, identity=_identity)
 
+    def run_batch_field_keys_tensor(self, values, offsets, names, kv=b"=", fs=b"\t", blanks=False, quote=None, escape=None, optional=(),
+                                    unquote=False, special=b"\n", only=None, ofs=None, sep_len=0, last_whole=False, keep_sep=True, suffix=b"",
+                                    out=None):
+        """Field mode by key (kx_run_batch_field_keys, keyed_records_model): the fields of record i — cut by the live `fs` bytes, or
+        with `blanks` into words — are key `kv` value pairs, and the program runs on the value of the first field whose key is each
+        of the bytes `names` (distinct, 1 to 16), each a whole input of its own; with `unquote` on its unquote_field_model value,
+        and the spelling of the output is spliced (requote_field_model with the `special` bytes).  A record that lacks a name not in
+        `optional` has status 2, fail_pos[i] = the mask of the names it has and fail_field[i] = 1 + the index of the first name it
+        lacks; a rejected value gives status 1 and fail_field[i] = 1 + the index of its name.  An accepted record writes its body with
+        every selected value replaced, then separator and suffix as run_batch_field_list_tensor; with `only` (a sequence of indices
+        into names, 1 to 16, in any order, repeats allowed) it writes the outputs of those names alone, joined by the 0 to 8 bytes
+        `ofs` — a name the record lacks writes nothing.  Returns the six tensors of run_batch_field_list_tensor."""
+        what = "run_batch_field_keys_tensor"
+        _check_batch_args(values, offsets)
+        for name, v in (("blanks", blanks), ("unquote", unquote), ("last_whole", last_whole), ("keep_sep", keep_sep)):
+            if not isinstance(v, bool):
+                raise TypeError("%s: %s must be True or False, not %s" % (what, name, type(v).__name__))
+        sep_len = _check_sep_len(sep_len)
+        given = list(names)
+        names, mask, _, c = _check_field_keys(what, given, optional, kv, None if blanks else fs, blanks, quote, escape)
+        if len(names) != len(given):
+            raise ValueError("%s: names are distinct" % what)
+        f = 0 if blanks else _check_fs(fs, quote, escape)
+        codec = proj = None
+        if only is not None:
+            only = [int(t) for t in only]
+            if not 1 <= len(only) <= FIELD_ITEMS_MAX or not all(0 <= t < len(names) for t in only):
+                raise ValueError("%s: only: 1 to %d indices into names" % (what, FIELD_ITEMS_MAX))
+            ofs = _check_ofs((b" " if blanks else bytes([f])) if ofs is None else ofs)
+        elif ofs is not None:
+            raise ValueError("%s: ofs= needs only=" % what)
+        if unquote:
+            q, e, special = _check_codec(what, quote, escape, special)
+            if blanks and len(special) > 7:
+                raise ValueError("%s: special must be 0 to 7 bytes (the tab is added), not %d" % (what, len(special)))
+            if only is not None:
+                _check_ofs_codec(what, ofs, q, e, special + (b"\t" if blanks else b""))
+            codec = KxFieldCodec(size=ctypes.sizeof(KxFieldCodec), n_special=len(special))
+            codec.special[:len(special)] = special
+        else:
+            q = None if quote is None else _one_byte(quote, "quote character")
+            e = None if escape is None else _one_byte(escape, "escape character")
+            if q is not None and q == e:
+                raise ValueError("escape character: %r is also the quote character" % bytes([e]))
+        if blanks:
+            _check_not_blank(quote, escape, special=special if unquote else b"")
+        if not isinstance(suffix, (bytes, bytearray)):
+            raise TypeError("%s: suffix must be bytes of length 0 to 8, not %s" % (what, type(suffix).__name__))
+        if len(suffix) > 8:
+            raise ValueError("%s: suffix must be 0 to 8 bytes, not %d" % (what, len(suffix)))
+        spec = KxBatchFieldList(size=ctypes.sizeof(KxBatchFieldList), n_ranges=0, fs=f, quote=-1 if q is None else q,
+                                escape=-1 if e is None else e, sep_len=sep_len, last_whole=1 if last_whole else 0,
+                                keep_sep=1 if keep_sep else 0, suffix_len=len(suffix))
+        spec.suffix[:len(suffix)] = bytes(suffix)
+        keys = field_keys_struct(names, mask, c, KX_KEYS_WORDS if blanks else 0)
+        if only is not None:
+            iarr, ni = _field_item_array([(0, t) for t in only])
+            proj = KxFieldProject(size=ctypes.sizeof(KxFieldProject), n_items=ni, items=iarr, ofs_len=len(ofs),
+                                  flags=KX_PROJECT_WORDS if blanks else 0)
+            proj.ofs[:len(ofs)] = ofs
+        return self._run_batch_call(what, values, offsets, out, None, spec, codec, proj=proj, keys=keys)
+
     def fields_kernel_stats(self):
         """kx_fields_stats: HIP-event times of field mode's own kernels, summed over this program's calls (collect_timing)."""
         st = KxFieldsKernelStats()
@@ -2131,6 +2389,26 @@ class Program:
         return items, _check_ofs(ofs)
 
     @staticmethod
+    def _check_keys(what, keys, optional, field, fields, fs, blanks, quote, escape, sep, rs, header):
+        """The `keys=` and `optional=` keywords of record mode: `keys` with `fields` (bytes names), not with `field` or `header` →
+        None, or (the distinct names, optional_mask, the items as indices, C): _check_field_keys's result."""
+        if keys is None:
+            if optional:
+                raise ValueError("%s: optional= needs keys=" % what)
+            return None
+        if header:
+            raise ValueError("%s: keys= cannot be combined with header=" % what)
+        if field is not None or fields is None:
+            raise ValueError("%s: keys= needs fields=, a sequence of bytes names" % what)
+        if not isinstance(blanks, bool):
+            raise TypeError("%s: blanks must be True or False, not %s" % (what, type(blanks).__name__))
+        if blanks and fs is not None:
+            raise ValueError("%s: blanks= cannot be combined with fs=" % what)
+        one = isinstance(rs, (bytes, bytearray)) and len(rs) == 1
+        return _check_field_keys(what, fields, optional, keys, None if blanks else b"\t" if fs is None else fs, blanks, quote, escape,
+                                 sep if rs is None else bytes(rs) if one else None)
+
+    @staticmethod
     def _check_rs_alone(rs, sep, quote, escape, what):
         """The `rs=` keyword of record mode: 1 to 8 bytes, with the default `sep` and neither `quote` nor `escape`."""
         rs = _check_rs(rs)
@@ -2141,7 +2419,7 @@ class Program:
         return rs
 
     def run_records(self, data, sep=b"\n", device=None, quote=None, escape=None, batch_actions=True, rs=None, chomp=False, ors=b"",
-                    field=None, fs=None, fields=None, unquote=False, blanks=False, only=False, ofs=None, header=0):
+                    field=None, fs=None, fields=None, unquote=False, blanks=False, only=False, ofs=None, header=0, keys=None, optional=()):
         """Record mode on bytes: every record of `data` (split after each `sep` byte, kx_split_records on the device) is a
         whole input.  Returns a list holding, per record, its output bytes or a MatchError (pos, stage).  With a `quote` byte
         a separator inside quotes ends no record (kx_split_records_quoted from parity 0).  With an `escape` byte an escaped
@@ -2169,9 +2447,16 @@ class Program:
         in their places — body, separator unless `chomp`, `ors`; with `only` their projection (kx_run_batch_field_header), or a
         NoFieldError.  `fields` may then hold bytes NAMES, resolved against the cells of record N (header_names_model,
         resolve_field_names): a name no cell has raises HeaderError; data with fewer than N records resolves nothing (under `only`
-        with names its records then give b"")."""
+        with names its records then give b"").  With `keys` (the key separator C, one byte; with `fields`, a sequence of bytes
+        NAMES; not with `header`) the fields are key C value pairs and the program runs on the value of the first field that has each
+        name for a key (kx_run_batch_field_keys, keyed_records_model): a record that lacks a name not in `optional` gives a
+        NoFieldError whose `field` is the first such name, a rejected value a MatchError whose `field` is its name; with `only` the
+        outputs come in the order of `fields`, and a name the record lacks gives nothing."""
         if not isinstance(data, (bytes, bytearray, memoryview)):
             raise TypeError("run_records: data must be bytes, not %s" % type(data).__name__)
+        keyed = self._check_keys("run_records", keys, optional, field, fields, fs, blanks, quote, escape, sep, rs, header)
+        if keyed is not None:
+            fields = [1] * len(keyed[2])                 # (a placeholder for the checks: the names select the fields)
         header, named = _check_header("run_records", header, fields)
         written = list(fields) if named else None
         if named:                                        # (a placeholder for the checks; the numbers come with record N)
@@ -2228,6 +2513,10 @@ class Program:
             ob = out.cpu().numpy().tobytes()
             ooff, status, fpos, fstage = ooff.tolist(), status.tolist(), fpos.tolist(), fstage.tolist()
             ffield = [None] * len(status) if len(res) < 6 else res[5].tolist()
+            if keyed is not None:
+                name = lambda i: keyed[0][ffield[i] - 1]                                  # noqa: E731
+                return [NoFieldError(fpos[i], name(i)) if status[i] == 2 else MatchError(fpos[i], fstage[i], name(i)) if status[i]
+                        else ob[ooff[i]:ooff[i + 1]] for i in range(len(status))]
             return [NoFieldError(fpos[i]) if status[i] == 2 else MatchError(fpos[i], fstage[i], ffield[i]) if status[i] else ob[ooff[i]:ooff[i + 1]]
                     for i in range(len(status))]
 
@@ -2260,7 +2549,12 @@ class Program:
                 return head
             offs = offs[nh:]
         with self._batch_actions_for_call(batch_actions):
-            if items is not None:
+            if keyed is not None:
+                res = self.run_batch_field_keys_tensor(
+                    v, offs, keyed[0], keys, fs, blanks, quote, escape, optional, unquote=unquote, special=sep_byte,
+                    only=keyed[2] if items is not None else None, ofs=ofs, sep_len=len(rs) if rs is not None else 1,
+                    last_whole=bool(tail and data), keep_sep=not chomp, suffix=ors)
+            elif items is not None:
                 res = self.run_batch_field_project_tensor(
                     v, offs, items, ofs, fs, blanks, quote, escape, unquote=unquote, special=sep_byte,
                     sep_len=len(rs) if rs is not None else 1, last_whole=bool(tail and data), keep_sep=not chomp, suffix=ors)
@@ -2285,7 +2579,8 @@ class Program:
         return head + unpack(res)
 
     def run_records_fd(self, in_fd, out_fd, sep=b"\n", report_fd=-1, quote=None, escape=None, batch_actions=True, rs=None, chomp=False,
-                       ors=b"", field=None, fs=None, fields=None, unquote=False, blanks=False, only=False, ofs=None, header=0):
+                       ors=b"", field=None, fs=None, fields=None, unquote=False, blanks=False, only=False, ofs=None, header=0, keys=None,
+                       optional=()):
         """kx_run_records_fd: the stream on in_fd in record mode, outputs to out_fd, one line per rejected record to report_fd
         (-1: none).  Returns kx_records_stats as a dict, with "rejected" = whether some record was rejected.  With a `quote`
         byte, kx_run_records_fd_quoted: a separator inside quotes ends no record.  With an `escape` byte,
@@ -2300,7 +2595,11 @@ class Program:
         With `blanks` (as in run_records), kx_run_records_fd_field_words: the fields are the words between live spaces and tabs.
         With `only` and `ofs` (as in run_records), kx_run_records_fd_field_project: only the selected fields' outputs are written.
         With `header` = N >= 1, kx_run_records_fd_table: the first N records are header records, and `fields` may hold bytes names of
-        the cells of record N; a name no cell has raises EngineError (KX_E_HEADER) with the library's message."""
+        the cells of record N; a name no cell has raises EngineError (KX_E_HEADER) with the library's message.  With `keys` and
+        `optional` (as in run_records), kx_run_records_fd_field_keys: the report lines name the field by its key."""
+        keyed = self._check_keys("run_records_fd", keys, optional, field, fields, fs, blanks, quote, escape, sep, rs, header)
+        if keyed is not None:
+            fields = [1] * len(keyed[2])                 # (a placeholder for the checks: the names select the fields)
         header, named = _check_header("run_records_fd", header, fields)
         written = list(fields) if named else None
         if named:                                        # (a placeholder for the checks; the library resolves the names)
@@ -2350,6 +2649,11 @@ class Program:
                         iarr, ni = _field_item_array(items)
                         name, args = "kx_run_records_fd_field_project", (ctypes.byref(o), iarr, ni, f, ofs, len(ofs),
                                                                          (KX_PROJECT_WORDS if blanks else 0) | (KX_PROJECT_UNQUOTE if unquote else 0))
+                if keyed is not None:
+                    kk = field_keys_struct(keyed[0], keyed[1], keyed[3], (KX_KEYS_WORDS if blanks else 0) | (KX_KEYS_UNQUOTE if unquote else 0) |
+                                           (KX_KEYS_ONLY if items is not None else 0))
+                    karr = (ctypes.c_uint32 * 16)(*keyed[2])
+                    name, args = "kx_run_records_fd_field_keys", (ctypes.byref(o), ctypes.byref(kk), f, karr, len(keyed[2]), ofs or b"", len(ofs or b""))
                 if header:                               # one entry point for every combination
                     tflags = (KX_TABLE_WORDS if blanks else 0) | (KX_TABLE_UNQUOTE if unquote else 0) | (KX_TABLE_ONLY if items is not None else 0)
                     titems = written if named else items if items is not None else fields if fields is not None else []
